@@ -10,25 +10,40 @@ are independent, so no collective touches the data path; the only
 collectives are the barrier around the timed region, the max over ranks of
 the elapsed time and an all-ranks parity flag (glusterfs_amd/dist.py).
 
-The JSON line also carries
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline
+figure needs: it generates and encodes the input, warms up, times the K
+steps, compares the decoded output with the input on the GPU (parity_ok),
+writes the output under --dump-outputs if given, and prints the JSON line.
+That line carries
+  ms_per_step   the wall time of the K timed steps / K, in milliseconds
   roofline      the decode kernel against the 8 TB/s HBM peak: algorithmic
                 bytes per launch (2*S: read k fragments = S, write S) over the
-                average launch time measured with HIP events on the launch
-                stream; `traffic` = PMC-measured HBM bytes per launch from the
-                committed rocprofv3 run (profiles/traffic.json)
+                average launch time of the same K steps, measured with HIP
+                events on the launch stream; `traffic` = PMC-measured HBM
+                bytes per launch from the committed rocprofv3 run
+                (profiles/traffic.json)
+Everything else is measured only with --full, which adds
+  fullsize_sha256_check  the SHA-256 fixture comparison described below
   cpu_baseline  the CPU oracle (oracle/, C restatement of the reference
                 algorithm) on the host's usable cores and on one thread:
                 BASELINE configs[0] (4+2 encode of 1 GiB) and the bench
                 workload (4+2 decode), rank 0 at N=1 only
   extra         (N=1) the other BASELINE configs measured the same way, a
                 copy calibration, PCIe-inclusive end-to-end rates and the
-                library's own CPU engine
+                library's own CPU engine; for N > 1 the per-N 16+4 encode /
+                self-heal / PCIe lines instead
+--extra / --no-extra, --no-cpu and --no-dist-extra narrow a --full run.
+
+--dump-outputs DIR writes what the last timed step decoded (the `out` buffer
+a caller of decode_device receives) as float32 / float64 .npy files, see
+dump_outputs().  The input is a fixed stream, so two builds run with the same
+arguments can be compared file for file.
 
 Input data is the xorshift64 stream of SURVEY.md 8(d), generated on the
 GPU (glusterfs_amd/synth.py); rank r of an N-GPU job owns the r-th slice of
-one stream.  Full-size results are checked against the SHA-256 fixtures of
-tests/golden/fullsize_sha256.json (oracle-generated in the container):
-input, every encoded fragment, and decode outputs (= the input).
+one stream.  With --full, full-size results are checked against the SHA-256
+fixtures of tests/golden/fullsize_sha256.json (oracle-generated in the
+container): input, every encoded fragment, and decode outputs (= the input).
 """
 import argparse
 import hashlib
@@ -46,6 +61,9 @@ HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 CHUNK = 512
 EXTRA_WARMUP = 20  # untimed launches before each `extra` config (extra_configs)
 SUSTAIN_MS = 150.0  # continuous load before the `sustained` headline figure
+DUMP_SEED = 20240607       # --dump-outputs: which bytes of a large output are kept
+DUMP_SAMPLE = 8 << 20      # ... and how many (float32: 32 MiB)
+DUMP_SUMS = 1 << 21        # ... and at most this many stripe-group sums (float64: 16 MiB)
 
 
 def parse():
@@ -56,9 +74,16 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--gib", type=float, default=1.0, help="user data per GPU per step")
-    ap.add_argument("--extra", dest="extra", action="store_true", default=None)
-    ap.add_argument("--no-extra", dest="extra", action="store_false")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the SHA-256 "
+                         "fixtures, the other BASELINE configs (`extra`), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's decoded output to DIR/<name>.npy")
+    ap.add_argument("--extra", dest="extra", action="store_true", default=None,
+                    help="--full: the `extra` configs also for N > 1")
+    ap.add_argument("--no-extra", dest="extra", action="store_false",
+                    help="--full: without the `extra` configs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: without the CPU baseline")
     ap.add_argument("--no-dist-extra", action="store_true",
                     help="N > 1: skip the per-N 16+4 encode / self-heal / PCIe lines")
     ap.add_argument("--heal-sweep", default=None, choices=("auto", "gpu", "cpu"),
@@ -144,8 +169,9 @@ def timed(torch, fn, steps, warmup, group=None, warm_ms=0.0):
 
 
 class Ctx:
-    def __init__(self, g, torch, dev, rank=0):
+    def __init__(self, g, torch, dev, rank=0, fixtures=True):
         self.g, self.torch, self.dev, self.rank = g, torch, dev, rank
+        self.fixtures = fixtures   # compare full-size results with the SHA-256 fixtures
         self.sp = torch.cuda.current_stream(dev).cuda_stream
         self.checks = {}
         self.warm_ms = 0.0     # time-based warm-up (extra / dist configs only)
@@ -171,7 +197,7 @@ class Ctx:
             frags = [torch.empty(nst * CHUNK, dtype=torch.uint8, device=self.dev) for _ in range(n)]
         L = self.g.ECMatrixList(k, n)
         L.encode_device(self.dev.index, self.sp, nst, data, frags)
-        fx = fixture(case, self.rank) if case else None
+        fx = fixture(case, self.rank) if case and self.fixtures else None
         if fx and fx["bytes"] == user and fx["k"] == k and fx["word0"] == w0:
             torch.cuda.synchronize()
             ok = sha_dev(data) == fx["data"]
@@ -199,7 +225,43 @@ def run_decode(c, k, n, nbytes, mask, steps, warmup, case=None, group=None, sus=
     ks = sustained(c, fn, steps) if sus else None
     ok = bool(c.torch.equal(out, data)) and c.checks.get("%s_r%d" % (case, c.rank), True)
     return dict(wall=wall, kernel_s=kt, kernel_s_sus=ks, ok=ok, user=nst * CHUNK * k, nst=nst,
-                frags=frags, rows=rows)
+                frags=frags, rows=rows, out=out)
+
+
+def dump_outputs(torch, dirname, rank, out, stripe):
+    """--dump-outputs: the decoded bytes of the last timed step, as a caller
+    of decode_device receives them in `out`, written as
+      decoded.npy              every byte, float32 -- when there are at most
+                               DUMP_SAMPLE of them; otherwise
+      decoded_sample.npy       the bytes at DUMP_SAMPLE positions drawn once
+                               from numpy's default_rng(DUMP_SEED), ascending,
+                               float32, and
+      decoded_stripe_sums.npy  the byte sum of every stripe (of groups of G
+                               consecutive stripes where there are more than
+                               DUMP_SUMS stripes), float64, exact -- so every
+                               output byte bears on the dump.
+    Ranks above 0 append _rank<r> to the names.  Returns the file names."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "_rank%d" % rank if rank else ""
+    n = out.numel()
+    files = {}
+    if n <= DUMP_SAMPLE:
+        files["decoded"] = out.cpu().numpy().astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+        pick = out[torch.from_numpy(idx).to(out.device)]
+        files["decoded_sample"] = pick.cpu().numpy().astype(np.float32)
+        sums = out.view(-1, stripe).sum(dim=1, dtype=torch.int64).cpu().numpy()
+        group = -(-len(sums) // DUMP_SUMS)
+        if group > 1:
+            sums = np.add.reduceat(sums, np.arange(0, len(sums), group))
+        files["decoded_stripe_sums"] = sums.astype(np.float64)
+    names = []
+    for name, a in files.items():
+        names.append(name + sfx + ".npy")
+        np.save(os.path.join(dirname, names[-1]), a)
+    return names
 
 
 def run_encode(c, k, n, nbytes, steps, warmup, case=None, group=None, sus=False, word0=None):
@@ -208,7 +270,7 @@ def run_encode(c, k, n, nbytes, steps, warmup, case=None, group=None, sus=False,
     fn = lambda: L.encode_device(c.dev.index, c.sp, nst, data, frags)  # noqa: E731
     wall, kt = timed(torch, fn, steps, warmup, group, c.warm_ms)
     ks = sustained(c, fn, steps) if sus else None
-    fx = fixture(case, c.rank) if case else None
+    fx = fixture(case, c.rank) if case and c.fixtures else None
     if fx and "frags" in fx and fx["bytes"] == nst * CHUNK * k:
         torch.cuda.synchronize()        # the timed launches rewrote the fragments
         ok = all(sha_dev(f) == h for f, h in zip(frags, fx["frags"]))
@@ -1044,7 +1106,7 @@ def main():
     placement = bind_rank(g, dev_index, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
     grp = Group()
     dev = torch.device("cuda", dev_index)
-    c = Ctx(g, torch, dev, grp.rank)
+    c = Ctx(g, torch, dev, grp.rank, fixtures=args.full)
     nbytes = int(args.gib * (1 << 30))
     if args.only:
         c.warm_ms = args.warm_ms
@@ -1084,8 +1146,10 @@ def main():
         "vs_baseline": None,
         "dtype": "u8",
         "data": "synthetic: xorshift64 stream of SURVEY 8(d), rank r = r-th slice, generated "
-                "and encoded on-GPU; input, fragments and output checked against the "
-                "oracle's full-size SHA-256 fixtures",
+                "and encoded on-GPU; " +
+                ("input, fragments and output checked against the oracle's full-size SHA-256 "
+                 "fixtures" if args.full else
+                 "output compared with the input on the GPU (SHA-256 fixtures: --full)"),
         "config": {
             "workload": "disperse 4+2 decode, 2 fragments missing (mask 0x3C), "
                         "%d MiB user data per GPU per step (BASELINE configs[1])" %
@@ -1111,14 +1175,18 @@ def main():
     }
     out["fullsize_sha256_check"] = c.checks.get("4+2_1GiB_r%d" % grp.rank)
     out["ranks"] = grp.gather(placement)
+    if args.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(torch, args.dump_outputs, grp.rank, r["out"],
+                                             CHUNK * k)
     del r
     torch.cuda.empty_cache()
-    extra = args.extra if args.extra is not None else grp.world == 1
+    # everything below is measured with --full only
+    extra = args.full and (args.extra if args.extra is not None else grp.world == 1)
     if extra:
         out["extra"] = extra_configs(c, args.steps, args.warmup)
-    elif grp.world > 1 and not args.no_dist_extra:
+    elif args.full and grp.world > 1 and not args.no_dist_extra:
         out["extra"] = dist_configs(c, grp, args.steps, args.warmup)
-    if grp.rank == 0 and grp.world == 1 and not args.no_cpu:
+    if args.full and grp.rank == 0 and grp.world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline()
         if extra:
             try:

@@ -32,7 +32,7 @@ def test_two_ranks_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-extra", "--no-cpu"]
+           "--full", "--no-extra", "--no-cpu"]     # --full: the SHA-256 fixture check
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]

@@ -77,7 +77,7 @@ def main(tag):
                      cb["one_thread_decode_GBps"], cb["one_thread_encode_GBps"], cb["value"],
                      cb["encode_1GiB_GBps"]))
     head = ('Latest N=1 numbers (MI355X, HEAD of round 2, `tools/gpu_round_end.sh`, tag `%s`). '
-            '"bench" = `bench.py --gpus 1 --steps 20 --warmup 5` event timing '
+            '"bench" = `bench.py --gpus 1 --steps 20 --warmup 5 --full` event timing '
             '(`profiles/%s/%s_bench.log`; `extra` configs 10 launches after 20); the same '
             'command\'s headline under `rocprofv3 --kernel-trace --stats` (`--no-extra --no-cpu`, '
             '`profiles/%s/bench_rocprof_kernel_stats.csv`): %d launches of the headline kernel '

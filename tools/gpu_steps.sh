@@ -24,10 +24,10 @@ for step in "$@"; do
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
     pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     pytest_new) run pytest_new 600 python -u -m pytest ${TESTS} -m gpu -x -v --timeout 120 --timeout-method thread ;;
-    bench) run bench 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    bench) run bench 400 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
     bench_rocprof) run bench_rocprof 300 bash -c "cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_bench_$TAG -o run --output-format csv -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-extra --no-cpu && python3 $R/tools/prof_filter.py $R/gpurun_out/prof_bench_$TAG ec_" ;;
-    rehearsal) run rehearsal 300 env EC_BENCH_BACKEND=gloo EC_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus 2 --steps 5 --warmup 1 ;;
-    rehearsal4) run rehearsal4 600 env EC_BENCH_BACKEND=gloo EC_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29561 bench.py --gpus 4 --steps 3 --warmup 1 ;;
+    rehearsal) run rehearsal 300 env EC_BENCH_BACKEND=gloo EC_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29555 bench.py --gpus 2 --steps 5 --warmup 1 --full ;;
+    rehearsal4) run rehearsal4 600 env EC_BENCH_BACKEND=gloo EC_BENCH_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29561 bench.py --gpus 4 --steps 3 --warmup 1 --full ;;
     profile) run profile 900 bash tools/profile.sh "$TAG" ${PROFILE_ARGS:-dec:4+2:3C 1 enc:4+2 1 enc:8+4 0.25 dec:8+4:FF0 0.25 enc:16+4 2 mixed:8+4 1 heal:8+4 1 dec:16+4:FFFF0 1 mixed:16+4:64 1 rmw:4+2 1 rmw:8+4 1 rmw:16+4 1} ;;
     kbench) run kbench 600 tools/kbench/kbench ${KBENCH_ARGS:-} ;;
     trace) run trace 600 bash tools/prof_trace.sh "$TAG" ${TRACE_ARGS:-dec:16+4:FFFF0 1 dec:4+2:3C 1} ;;
