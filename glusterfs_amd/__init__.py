@@ -18,6 +18,7 @@ from .ec_method import (  # noqa: F401
     host_registered,
     jit_compile_check,
     jit_prepare,
+    jit_source,
     jit_stats,
     inject_device_faults,
     inverse_matrix,

@@ -758,6 +758,23 @@ extern "C" int ecd_jit_prepare(uint32_t k, uint32_t rows, const uint8_t *coef)
     return lookup(key) ? 0 : -ENOSPC;
 }
 
+extern "C" int ecd_jit_source(uint32_t k, uint32_t rows, const uint8_t *coef, char *buf, size_t len)
+{
+    if (k < 1 || k > ECJ_MAX || rows < 2 || rows > ECJ_MAX || !coef)
+        return -EINVAL;
+    Key key;
+    key.k = k;
+    key.rows = rows;
+    memcpy(key.coef, coef, (size_t)k * rows);
+    const std::string src = source_of(key, nullptr);
+    if (buf && len) {
+        const size_t n = src.size() < len - 1 ? src.size() : len - 1;
+        memcpy(buf, src.data(), n);
+        buf[n] = '\0';
+    }
+    return (int)(src.size() + 1);
+}
+
 extern "C" int ecd_jit_compile_check(uint32_t k, uint32_t rows, const uint8_t *coef, uint32_t *ops,
                                  char *log, size_t log_len)
 {

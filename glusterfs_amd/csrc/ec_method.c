@@ -1514,6 +1514,20 @@ ec_method_jit_compile_check(uint32_t k, uint32_t rows, const uint8_t *coef, uint
     return ecd_jit_compile_check(k, rows, coef, ops, log, sizeof log);
 }
 
+/* A weak reference: host-only builds of this file around a device-layer stub
+ * (tests/c/ecd_stub.c: no generator there) link without it, and the call is
+ * then -ENOSYS; the library always links ec_jit.hip's definition. */
+extern int ecd_jit_source(uint32_t k, uint32_t rows, const uint8_t *coef, char *buf, size_t len)
+    __attribute__((weak));
+
+int32_t
+ec_method_jit_source(uint32_t k, uint32_t rows, const uint8_t *coef, char *buf, size_t len)
+{
+    if (!ecd_jit_source)
+        return -ENOSYS;
+    return ecd_jit_source(k, rows, coef, buf, len);
+}
+
 /* disperse.cpu-extensions (ec.c:1786-1794) -> engine.  The reference maps
  * none to portable C and x64 / sse / avx to its JIT back ends, auto to the
  * best of them (ec-code.c:59-69, 977-1060).  Here auto (and hip) select the

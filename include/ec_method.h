@@ -418,12 +418,16 @@ void ec_method_pool_stats(ec_method_pool_stats_t *stats);
  * reference's per-row JIT, ec-code.c:722-809).  A device-buffer combine with
  * one erasure pattern of a wide code (k >= 12 data and >= 12 output rows,
  * e.g. a 16+4 decode; >= EC_MI355X_JIT_MIN_STRIPES stripes, default 1024)
- * queues its coefficient matrix for compilation (hiprtc, opened with dlopen;
- * one library thread, ~1-2 s) as one straight-line XOR program over the
- * whole matrix, and runs the shipped kernel until that code exists; later
- * calls of the matrix run it.  Results are identical either way.
- * EC_MI355X_JIT=0 turns this off, EC_MI355X_JIT_SYNC=1 compiles on the
- * calling thread.  Counters: */
+ * queues its coefficient matrix for compilation as one straight-line XOR
+ * program over the whole matrix, and runs the shipped kernel until that code
+ * exists; later calls of the matrix run it.  The compiler is a child process
+ * (ec_jitc, installed next to the library; it alone loads hiprtc), one per
+ * matrix, ~1-2 s; one library thread starts it and waits for it.  That thread
+ * is neither stopped nor joined at exit: a process that exits mid-compile
+ * leaves the child to finish on its own, and nothing of the compiler lives
+ * in the client's address space.  Results are identical either way.
+ * EC_MI355X_JIT=0 turns this off, EC_MI355X_JIT_SYNC=1 starts and waits for
+ * the compiler on the calling thread.  Counters: */
 typedef struct {
     uint64_t compiled;    /* matrices compiled                          */
     uint64_t failed;      /* compilations that failed (shipped kernel)  */
@@ -445,6 +449,14 @@ int32_t ec_method_jit_prepare(uint32_t k, uint32_t rows, const uint8_t *coef);
  * device (tests). */
 int32_t ec_method_jit_compile_check(uint32_t k, uint32_t rows, const uint8_t *coef,
                                     uint32_t *ops);
+/* The kernel source the compiler would read for a rows x k matrix, as text:
+ * copies at most len - 1 bytes and a terminating 0 into buf (buf may be NULL
+ * when len is 0) and returns the bytes needed, the terminator included, or
+ * -EINVAL for the geometries ec_method_jit_compile_check rejects.  Pure text
+ * generation: needs no compiler and no device (tests run the programs of
+ * this text on the host, tests/test_jit_program.py). */
+int32_t ec_method_jit_source(uint32_t k, uint32_t rows, const uint8_t *coef, char *buf,
+                             size_t len);
 
 /* Host-side matrix helpers, exported for tests and tools: the n x k encode
  * matrix (ec-method.c:22-36) and the k x k inverse for ascending rows

@@ -14,7 +14,21 @@ matrix once the code exists.  Every result is compared with the oracle:
     shipped kernel while a library thread compiles, later calls the
     compiled one -- exact both ways;
   * a process exiting while its matrix compiles exits cleanly;
-  * EC_MI355X_JIT=0: never compiled, never launched.
+  * EC_MI355X_JIT=0: never compiled, never launched;
+  * the kernel body's edges, with EC_MI355X_JIT_MIN_STRIPES=1 so that counts
+    below one 4-stripe tile reach the compiled kernel: 1, 2, 3, 4, 5 and 9
+    stripes through both store forms (a decode's contiguous run, and the
+    512-byte row runs of a 16 -> 13 heal and a 12-row encode), outputs
+    pre-filled and followed by a guard stripe that must stay untouched; the
+    same through the non-temporal entry (EC_MI355X_LDSNT=1); odd row counts
+    (13+3 and 15+2 decodes, 13 and 15 rows of 16 inputs) and more rows than
+    inputs (16 rows of 12+16); every fragment at its own byte offset; an
+    output that is only 8-byte aligned (ineligible: the shipped kernel codes
+    it, launches unchanged); four threads meeting one matrix for the first
+    time; a caller's stream.  Every case asserts the exact jit_stats deltas,
+    so a silent fall-back to the shipped kernel cannot pass for the compiled
+    one.  (The programs themselves are checked on the CPU for many more
+    matrices, tests/test_jit_program.py.)
 Each case runs in its own process through the C ABI (the settings are read
 once per process)."""
 import os
@@ -131,8 +145,9 @@ print("ok", s)
 """
 
 # a process that exits while its matrix is still being compiled: the compile
-# thread is joined at exit (a compile running through the compiler's static
-# destructors would crash the exit)
+# runs in a child process (ec_jitc), and the library thread that waits for it
+# is neither stopped nor joined at exit, so the exit tears nothing down under
+# a compile (the child finishes on its own or is orphaned)
 EXIT = COMMON + r"""
 with g.ECMatrixList(16, 20) as L:
     decode_check(L, 16, 20, 2048, 0xFFFF0)
@@ -145,6 +160,202 @@ with g.ECMatrixList(16, 20) as L:
         decode_check(L, 16, 20, 2048, 0xFFFF0)
 s = g.jit_stats()
 assert s["compiled"] == 0 and s["launches"] == 0 and s["lookups"] == 0, s
+print("ok")
+"""
+
+
+# ---- the body's edges (EC_MI355X_JIT_MIN_STRIPES=1, EC_MI355X_JIT_SYNC=1) ----
+EDGE_COMMON = COMMON + r"""
+GUARD = 0xA5
+def guarded(nbytes, guard, off=0):
+    # nbytes of output pre-filled with 0xA5, a guard of `guard` bytes behind it
+    raw = torch.empty(off + nbytes + guard, dtype=torch.uint8, device="cuda")
+    raw.fill_(GUARD)
+    return raw[off:]
+def guard_ok(t, nbytes, what):
+    tail = t[nbytes:].cpu().numpy()
+    assert tail.size and (tail == GUARD).all(), ("guard overwritten", what)
+def delta(s0):
+    s1 = g.jit_stats()
+    return {k: s1[k] - s0[k] for k in s1}
+
+def decode_edge(L, k, nst, mask, offs=None, out_off=0, stream=None):
+    rows = O.mask_rows(mask)
+    frags = [rb(512 * nst) for _ in rows]
+    out = guarded(512 * k * nst, 512 * k, out_off)
+    assert out.data_ptr() % 16 == out_off
+    L.decode_batch(nst, mask, rows, [dev(f, offs[i] if offs else 0) for i, f in enumerate(frags)],
+                   out)
+    exp = O.decode(k, rows, frags)
+    assert np.array_equal(out[:exp.size].cpu().numpy(), exp), ("dec", k, nst, hex(mask))
+    guard_ok(out, exp.size, ("dec", k, nst))
+
+def heal_edge(L, k, n, nst, mask, target):
+    # the fused heal of non-codeword fragments: encode(decode(good)) rows
+    rows = O.mask_rows(mask)
+    frags = [rb(512 * nst) for _ in rows]
+    tgt = [b for b in range(n) if (target >> b) & 1]
+    outs = [guarded(512 * nst, 512) for _ in tgt]
+    L.heal_device(0, None, nst, mask, [dev(f) for f in frags], target, outs)
+    g.sync_device(0)
+    want = O.encode(k, n, O.decode(k, rows, frags))
+    for o, b in zip(outs, tgt):
+        assert np.array_equal(o[:512 * nst].cpu().numpy(), want[b]), ("heal", nst, b)
+        guard_ok(o, 512 * nst, ("heal", nst, b))
+
+def rows_edge(L, k, n, nst, rm):
+    data = rb(512 * k * nst)
+    want = O.encode(k, n, data)
+    outs = [guarded(512 * nst, 512) if (rm >> i) & 1 else None for i in range(n)]
+    L.encode_rows_device(0, None, nst, dev(data), rm, outs)
+    g.sync_device(0)
+    for i in range(n):
+        if outs[i] is not None:
+            assert np.array_equal(outs[i][:512 * nst].cpu().numpy(), want[i]), ("rows", nst, i)
+            guard_ok(outs[i], 512 * nst, ("rows", nst, i))
+
+HEAL_MASK = 0x2AAB5555                         # 16 of the 31 bricks of 16+15
+assert bin(HEAL_MASK).count("1") == 16
+HEAL_13 = [b for b in range(31) if not (HEAL_MASK >> b) & 1][:13]
+HEAL_TARGET = sum(1 << b for b in HEAL_13)
+"""
+
+# ns == 1 tiles, counts below one tile, both store forms: three matrices
+RAGGED = EDGE_COMMON + r"""
+COUNTS = (1, 2, 3, 4, 5, 9)
+s0 = g.jit_stats()
+with g.ECMatrixList(16, 20) as L:
+    for nst in COUNTS:
+        decode_edge(L, 16, nst, 0xF3FF3)                 # contiguous run store
+with g.ECMatrixList(16, 31) as L:
+    for nst in COUNTS:
+        heal_edge(L, 16, 31, nst, HEAL_MASK, HEAL_TARGET)  # 13 rows, 512-byte row runs
+with g.ECMatrixList(16, 28) as L:
+    for nst in COUNTS:
+        rows_edge(L, 16, 28, nst, sum(1 << i for i in range(16, 28)))
+d = delta(s0)
+print("JIT", d)
+assert d["failed"] == 0 and d["compiled"] == 3, d
+assert d["lookups"] == 3 * len(COUNTS) and d["launches"] == 3 * len(COUNTS), d
+print("ok")
+"""
+
+# odd row counts (uneven halves), k of 13 and 15, rows > k: five matrices
+SHAPES = EDGE_COMMON + r"""
+nst = 9
+s0 = g.jit_stats()
+with g.ECMatrixList(13, 16) as L:
+    decode_edge(L, 13, nst, 0xDFF6)                      # k = rows = 13
+with g.ECMatrixList(15, 17) as L:
+    decode_edge(L, 15, nst, 0x1FDFB)                     # k = rows = 15
+with g.ECMatrixList(16, 31) as L:
+    heal_edge(L, 16, 31, nst, HEAL_MASK, HEAL_TARGET)    # 16 -> 13
+    rows_edge(L, 16, 31, nst, sum(1 << i for i in range(16, 31)))   # 16 -> 15
+with g.ECMatrixList(12, 28) as L:
+    rows_edge(L, 12, 28, nst, sum(1 << i for i in range(12, 28)))   # 12 -> 16, in_stride 512 * 12
+d = delta(s0)
+print("JIT", d)
+assert d["failed"] == 0 and d["compiled"] == 5 and d["lookups"] == 5 and d["launches"] == 5, d
+print("ok")
+"""
+
+ALIGN = EDGE_COMMON + r"""
+s0 = g.jit_stats()
+with g.ECMatrixList(16, 20) as L:
+    # every fragment at its own byte offset 1..15: LDS-DMA reads them in place
+    for nst in (9, 130):
+        decode_edge(L, 16, nst, 0xFFF0F, offs=[1 + i % 15 for i in range(16)])
+    d = delta(s0)
+    assert d["failed"] == 0 and d["compiled"] == 1 and d["lookups"] == 2 and d["launches"] == 2, d
+    # the output 8 bytes past a 16-byte boundary: not eligible (16-byte lane
+    # stores), the shipped kernel codes the call
+    for nst in (9, 130):
+        decode_edge(L, 16, nst, 0xFFF0F, out_off=8)
+    d2 = delta(s0)
+    assert d2["failed"] == 0 and d2["compiled"] == 1 and d2["lookups"] == 2, d2
+    assert d2["launches"] == 2, d2
+print("ok", d2)
+"""
+
+# four threads meet one matrix for the first time, each on its own
+# (per-thread) stream: the first to arrive compiles, the others run the
+# shipped kernel until the code exists.  All threads pass a barrier after
+# their first call, so the 8 later calls are made after the compile finished
+# and must launch the compiled kernel, as must the compiling thread's first.
+THREADS = EDGE_COMMON + r"""
+import threading
+k, nst, mask = 16, 64, 0x7EBFE
+rows = O.mask_rows(mask)
+frags = [rb(512 * nst) for _ in rows]
+dfr = [dev(f) for f in frags]
+exp = O.decode(k, rows, frags)
+outs = [[guarded(512 * k * nst, 512 * k) for _ in range(3)] for _ in range(4)]
+torch.cuda.synchronize()
+start, first_done = threading.Barrier(4), threading.Barrier(4)
+errors = []
+s0 = g.jit_stats()
+with g.ECMatrixList(16, 20) as L:
+    def worker(t):
+        try:
+            start.wait()
+            for c in range(3):
+                L.decode_device(0, None, nst, mask, dfr, outs[t][c])
+                g.sync_device(0)
+                if c == 0:
+                    first_done.wait()
+        except Exception as e:
+            errors.append(repr(e))
+            start.abort()
+            first_done.abort()
+    th = [threading.Thread(target=worker, args=(t,)) for t in range(4)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+assert not errors, errors
+for t in range(4):
+    for c in range(3):
+        assert np.array_equal(outs[t][c][:exp.size].cpu().numpy(), exp), ("thread", t, "call", c)
+        guard_ok(outs[t][c], exp.size, ("thread", t, c))
+d = delta(s0)
+print("JIT", d)
+assert d["failed"] == 0 and d["compiled"] == 1 and d["lookups"] == 12, d
+assert d["launches"] >= 4, d
+assert 9 <= d["launches"] <= 12, d
+print("ok")
+"""
+
+# a caller's stream: the fragments are written on a non-default torch stream
+# behind work that keeps it busy, the decode is queued on that stream's
+# handle and the result read back on it, with no device-wide synchronisation
+# in between; a kernel launched on any other stream would read the zeros the
+# fragment buffers held before
+STREAM = EDGE_COMMON + r"""
+k, nst, mask = 16, 2048, 0xBDFF5
+rows = O.mask_rows(mask)
+frags = [rb(512 * nst) for _ in rows]
+src = [dev(f) for f in frags]
+dst = [torch.zeros(512 * nst, dtype=torch.uint8, device="cuda") for _ in rows]
+busy = torch.zeros(256 << 20, dtype=torch.uint8, device="cuda")
+exp = O.decode(k, rows, frags)
+torch.cuda.synchronize()
+s0 = g.jit_stats()
+st = torch.cuda.Stream()
+with g.ECMatrixList(16, 20) as L:
+    L.decode_batch(nst, mask, rows, src, guarded(512 * k * nst, 512 * k))   # compiles the matrix
+    with torch.cuda.stream(st):
+        out = guarded(512 * k * nst, 512 * k)
+        for _ in range(8):
+            busy.add_(1)
+        for a, b in zip(dst, src):
+            a.copy_(b)
+        L.decode_device(0, st.cuda_stream, nst, mask, dst, out)
+        got = out.cpu().numpy()
+assert np.array_equal(got[:exp.size], exp)
+assert (got[exp.size:] == GUARD).all()
+d = delta(s0)
+print("JIT", d)
+assert d["failed"] == 0 and d["compiled"] == 1 and d["lookups"] == 2 and d["launches"] == 2, d
 print("ok")
 """
 
@@ -176,3 +387,31 @@ def test_jit_exit_while_compiling():
 
 def test_jit_off():
     _run(OFF, EC_MI355X_JIT="0")
+
+
+EDGE_ENV = dict(EC_MI355X_JIT_SYNC="1", EC_MI355X_JIT_MIN_STRIPES="1")
+
+
+def test_jit_ragged_and_sub_tile_counts():
+    print(_run(RAGGED, **EDGE_ENV))
+
+
+def test_jit_non_temporal_entry_small_counts():
+    """The same counts through ec_jit_combine_nt (aligned inputs)."""
+    print(_run(RAGGED, EC_MI355X_LDSNT="1", **EDGE_ENV))
+
+
+def test_jit_odd_rows_and_rows_above_k():
+    print(_run(SHAPES, **EDGE_ENV))
+
+
+def test_jit_fragment_offsets_and_ineligible_output():
+    print(_run(ALIGN, **EDGE_ENV))
+
+
+def test_jit_first_sight_from_four_threads():
+    print(_run(THREADS, **EDGE_ENV))
+
+
+def test_jit_callers_stream():
+    print(_run(STREAM, **EDGE_ENV))
