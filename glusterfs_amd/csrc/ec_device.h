@@ -66,6 +66,14 @@ int ecd_encode_vander(int device, void *stream, uint32_t k, uint32_t n,
                       uint64_t nstripes, const void *in, void *const *out);
 /* Generic combination (decode, mixed decode, generic encode, heal). */
 int ecd_combine(int device, void *stream, const ecd_combine_desc_t *d);
+/* Consistency check (ec_method_verify_device): d is the heal combination
+ * that predicts the fragments of d->rows bricks from its k inputs (one
+ * pattern in d->pat, in_stride 512; its outputs are unused), check[r] the
+ * stored fragment of row r and check_brick[r] its brick index.  bad[t]
+ * (device memory, one dword per stripe, all written) gets bit check_brick[r]
+ * set where stripe t's stored chunk of row r differs from the prediction. */
+int ecd_verify(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
+               const uint8_t *check_brick, uint32_t *bad);
 int ecd_sync(int device, void *stream);
 
 /* ---- host-memory entry points: stripes are partitioned across `ndev`

@@ -1618,6 +1618,17 @@ int ecd_combine(int device, void *stream, const ecd_combine_desc_t *d)
     return ecdk_combine(pick_stream(stream), d);
 }
 
+int ecd_verify(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
+               const uint8_t *check_brick, uint32_t *bad)
+{
+    if (ecd_device_count() <= device || device < 0)
+        return -ENODEV;
+    DeviceGuard dg;
+    clear_stale_error();
+    HIPCHK(hipSetDevice(g_dev_ids[device]));
+    return ecdk_verify(pick_stream(stream), d, check, check_brick, bad);
+}
+
 int ecd_sync(int device, void *stream)
 {
     if (ecd_device_count() <= device || device < 0)

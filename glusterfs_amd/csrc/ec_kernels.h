@@ -18,6 +18,9 @@ int ecdk_encode_vander(hipStream_t s, uint32_t k, uint32_t n, uint64_t nstripes,
 int ecdk_combine(hipStream_t s, const ecd_combine_desc_t *d);
 /* the same on pinned host memory (host-buffer path, zero-copy over PCIe) */
 int ecdk_combine_host(hipStream_t s, const ecd_combine_desc_t *d);
+/* consistency check of ecd_verify (ec_verify_n) */
+int ecdk_verify(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                const uint8_t *check_brick, uint32_t *bad);
 /* Partial-stripe writes: materialise bytes [o0, o0+n) (n % 16 == 0) of the
  * virtual input {head[0:b1) | user[0:b2-b1) | tail[...]} into dst, and the
  * fused Vandermonde encode that reads interior stripes from user directly. */

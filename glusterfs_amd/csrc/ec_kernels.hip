@@ -14,6 +14,8 @@
  *            8-stripe ec_combine, 16 waves (two blocks fill a CU's 32 wave
  *            slots); both stage by LDS-DMA into a plane-major tile and
  *            multiply by a jump into the searched XOR programs
+ *   verify   the consistency check: ec_verify_n, the narrow tile with the
+ *            check fragments staged beside the basis, 4 bytes out per stripe
  *   stores   non-temporal on every device-path kernel except the 2+1 / 4+2
  *            register encoders (profiles/kbench_r01_nts.log)
  *   staging  LDS-DMA loads non-temporal for calls whose input exceeds the
@@ -867,6 +869,82 @@ int ecdk_combine(hipStream_t s, const ecd_combine_desc_t *d)
             return 0;
     }
     return combine_any<true>(s, d);
+}
+
+/* ------------------------------------------- consistency check (scrub) */
+
+namespace {
+
+template <int K, int NW, int LA>
+int launch_verify(hipStream_t s, const VerifyArgs &a)
+{
+    const uint64_t g = (a.nstripes + 3) / 4;
+    if (g == 0)
+        return 0;
+    if (g > 0x7fffffffull)
+        return -EINVAL;
+    /* at most 31 inputs (ecdk_verify): 62 KiB + 16, under the 64 KiB a launch
+     * takes without raising the kernel's dynamic LDS limit */
+    const size_t lds = verify_n_lds(a.k + a.rows);
+    hipLaunchKernelGGL((ec_verify_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
+    return launch_ok("launch_verify");
+}
+
+/* the k -> K buckets and wave counts of launch_combine_k's narrow tiles;
+ * k > 8 runs 8 waves (two 62 KiB tiles of a 16+15 volume share a CU) */
+template <int LA>
+int launch_verify_k(hipStream_t s, const VerifyArgs &a)
+{
+    if (a.k <= 4)
+        return launch_verify<4, 4, LA>(s, a);
+    if (a.k <= 8)
+        return a.nstripes <= (1u << 17) ? launch_verify<8, 8, LA>(s, a)
+                                        : launch_verify<8, 4, LA>(s, a);
+    return launch_verify<16, 8, LA>(s, a);
+}
+
+} // namespace
+
+/* d: the heal combination of the check rows (k inputs, d->rows coefficient
+ * rows, one pattern in d->pat); check[r] / check_brick[r]: the stored
+ * fragment and brick index of row r; bad: nstripes device dwords. */
+int ecdk_verify(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                const uint8_t *check_brick, uint32_t *bad)
+{
+    VerifyArgs a;
+    if (d->k == 0 || d->k > ECD_MAX_K || d->rows == 0 || d->k + d->rows >= ECD_MAX_ROWS ||
+        d->npatterns != 1 || d->pat_ext || d->group_pattern ||
+        d->pat_bytes < d->k + d->rows * d->k || d->in_stride != ECD_CHUNK || !check ||
+        !check_brick || !bad || ((uintptr_t)bad & 3u))
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    a.k = d->k;
+    a.kw = (d->k + 3) / 4;
+    a.rows = d->rows;
+    a.nstripes = d->nstripes;
+    a.bad = bad;
+    if (a.kw * a.rows > kMaxPatWords)
+        return -EINVAL;
+    uintptr_t o = 0;
+    for (u32 p = 0; p < a.k; ++p) {
+        const uint8_t src = d->pat[p];
+        if (src >= ECD_MAX_ROWS || !d->in_base[src])
+            return -EINVAL;
+        a.in[p] = static_cast<const uint8_t *>(d->in_base[src]);
+        o |= (uintptr_t)a.in[p];
+    }
+    for (u32 r = 0; r < a.rows; ++r) {
+        if (!check[r] || check_brick[r] >= 32)
+            return -EINVAL;
+        a.in[a.k + r] = static_cast<const uint8_t *>(check[r]);
+        o |= (uintptr_t)check[r];
+        a.brick[r >> 2] |= (u32)check_brick[r] << ((r & 3u) * 8u);
+        for (u32 p = 0; p < a.k; ++p)
+            a.coef[r * a.kw + (p >> 2)] |= (u32)d->pat[a.k + r * a.k + p] << ((p & 3u) * 8u);
+    }
+    /* the staging policy of ecdk_combine, by the bytes the call reads */
+    const bool nt = nt_staging(a.nstripes * (a.k + a.rows) * ECD_CHUNK) && (o & 15u) == 0;
+    return nt ? launch_verify_k<kLdsDmaNT>(s, a) : launch_verify_k<kLdsDmaDefault>(s, a);
 }
 
 /* Host-buffer combines with k <= 8 run the persistent double-buffered

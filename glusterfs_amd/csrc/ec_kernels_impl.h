@@ -1473,6 +1473,99 @@ constexpr size_t combine_n_lds(int k)
     return (size_t)k * 4 * ECD_CHUNK + (WOT ? (size_t)NW * (4 / WOT) * ECD_CHUNK : 0);
 }
 
+/* ---------------------------------------------- consistency check (scrub) */
+
+/* Kernel arguments of ec_verify_n: the k basis fragments and the check
+ * fragments as one input list (in[k + r] is the stored fragment of row r),
+ * the rows' coefficients one word-aligned row each as in CombineArgs, and
+ * the brick index of every row, a byte each -- all read by scalar loads. */
+struct VerifyArgs {
+    const uint8_t *in[ECD_MAX_ROWS];
+    u32 *bad;
+    uint64_t nstripes;
+    u32 k, kw, rows, pad;
+    u32 brick[ECD_MAX_ROWS / 4];
+    u32 coef[kMaxPatWords];
+};
+
+/* ec_method_verify_device: do the stored fragments of `rows` bricks agree
+ * with what the k basis fragments imply?  The narrow combine's shape (T = 4
+ * stripes per block, 16 lanes per chunk, one dword column of all 8 planes
+ * per lane) with the check fragments staged beside the basis: the tile is
+ * (k + rows) * 2 KiB, then one u32 flag per stripe.  A wave item is one row
+ * for the 4 stripes: predict the row's chunk (the heal product), XOR the
+ * stored chunk's planes in from LDS, OR the 8 words; the 16 lanes of a
+ * stripe vote by ballot and one of them ORs the row's brick bit into the
+ * stripe's flag in LDS.  Each flag leaves by one plain dword store, so
+ * nothing is pre-zeroed and there are no global atomics; stripes past
+ * nstripes are neither staged nor stored. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_verify_n(const VerifyArgs a)
+{
+    constexpr u32 T = 4;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 tid = threadIdx.x;
+    const u32 k = a.k, ni = a.k + a.rows;
+    const uint64_t t0 = (uint64_t)blockIdx.x * T;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
+    if (tid < T)
+        flags[tid] = 0;
+    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        return a.in[p] + st * ECD_CHUNK;
+    }, ni, t0, a.nstripes, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    const uint8_t *col = lds + cs * 64u + cc * 4u;
+    const bool live = t0 + cs < a.nstripes;
+    for (u32 r = wave; r < a.rows; r += NW) {
+        const u32 rw = a.kw * r;
+        const u32 w0 = a.coef[rw];
+        const u32 w1 = K > 4 ? a.coef[rw + 1] : 0u;
+        const u32 w2 = K > 8 ? a.coef[rw + 2] : 0u;
+        const u32 w3 = K > 12 ? a.coef[rw + 3] : 0u;
+        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
+        u32 acc[8][1], y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            acc[b][0] = 0;
+#pragma unroll 1
+        for (u32 p = 0; p < k; ++p) {
+            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+            cl = (cl >> 8) | (ch << 56);
+            ch >>= 8;
+            if (c == 0)
+                continue;
+            const uint8_t *src = col + p * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+            ecgf::mul_xor_jt<1>(c, acc, y);
+        }
+        /* prediction ^ stored chunk: any bit left is a mismatch */
+        const uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
+        u32 d = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(chk + (u32)b * (T * 64u));
+        const uint64_t vote = __ballot(live && d != 0);
+        const u32 brick = __builtin_amdgcn_readfirstlane((a.brick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
+        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
+            atomicOr(&flags[cs], 1u << brick);
+    }
+    __syncthreads();
+    if (tid < T && t0 + tid < a.nstripes)
+        a.bad[t0 + tid] = flags[tid];
+}
+
+/* dynamic LDS of an ec_verify_n launch: the tile and the 4 stripe flags */
+constexpr size_t verify_n_lds(u32 inputs)
+{
+    return (size_t)inputs * 4 * ECD_CHUNK + 4 * sizeof(u32);
+}
+
 /* Zero-copy variant for the host-buffer path, where every input and output
  * lives in pinned host memory and the CUs read and write it over PCIe
  * (ec_device.hip run_pipeline).  There the link, not HBM or the VALU, is the

@@ -2637,6 +2637,150 @@ ecm_heal_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask,
                        pat, NULL, 0);
 }
 
+/* ------------------------------------------- consistency check (scrub) */
+
+/* A host-only build links a stand-in of the device layer that may lack the
+ * check's device entry (tests/c/ecd_stub.c): the reference is weak, and
+ * without the symbol ec_method_verify_device is -ENODEV. */
+extern __typeof__(ecd_verify) ecd_verify __attribute__((weak));
+
+#define ECM_VERIFY_STRIPES 32u /* stripes predicted per pass of the host check */
+
+/* Arguments both entry points share: the masks, the pointer arrays and the
+ * alignment of bad[].  rows[] gets the bricks of mask, bricks[] / *nc those
+ * of check_mask. */
+static int
+verify_args(ec_matrix_list_t *list, uintptr_t mask, const void *const *in, uintptr_t check_mask,
+            const void *const *check, const uint32_t *bad, uint32_t *rows, uint8_t *bricks,
+            uint32_t *nc)
+{
+    uint32_t i, c = 0;
+
+    if (!list || !CTX(list) || !in || !check || !bad || ((uintptr_t)bad & 3u))
+        return -EINVAL;
+    rows_from_mask(mask, rows);
+    if (!mask_rows_ok(list, mask, rows))
+        return -EINVAL;
+    if (check_mask == 0 || (check_mask >> list->rows) != 0 || (check_mask & mask) != 0)
+        return -EINVAL;
+    for (i = 0; i < list->rows; i++)
+        if ((check_mask >> i) & 1)
+            bricks[c++] = (uint8_t)i;
+    *nc = c;
+    return 0;
+}
+
+static int32_t
+ecm_verify_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask, const void *const *in,
+                uintptr_t check_mask, const void *const *check, uint32_t *bad, uint64_t *nbad)
+{
+    ecd_combine_desc_t d;
+    uint32_t rows[ECM_MAX_K], nc = 0, nt = 0, p, r, flag;
+    uint8_t bricks[ECM_MAX_N];
+    uint64_t s0, t, n, count = 0;
+    uint8_t *scratch;
+    int rc;
+
+    rc = verify_args(list, mask, in, check_mask, check, bad, rows, bricks, &nc);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    /* host entry point: device buffers go to _device */
+    for (p = 0; p < list->columns; p++)
+        if (!in[p] || ecd_ptr_device(in[p]) >= 0)
+            return -EINVAL;
+    for (r = 0; r < nc; r++)
+        if (!check[r] || ecd_ptr_device(check[r]) >= 0)
+            return -EINVAL;
+    if (ecd_ptr_device(bad) >= 0)
+        return -EINVAL;
+    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+    rc = heal_pattern(list, mask, rows, check_mask, d.pat, &nt);
+    if (rc)
+        return rc;
+    /* the CPU engine predicts a few dozen stripes of the check bricks into
+     * scratch, then every chunk is compared with the stored one */
+    scratch = (uint8_t *)malloc((size_t)ECM_VERIFY_STRIPES * nt * EC_METHOD_CHUNK_SIZE);
+    if (!scratch)
+        return -ENOMEM;
+    d.k = list->columns;
+    d.rows = nt;
+    d.npatterns = 1;
+    d.pat_bytes = d.k + nt * d.k;
+    d.in_stride = EC_METHOD_CHUNK_SIZE;
+    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    for (r = 0; r < nt; r++)
+        d.out_base[r] = scratch + (size_t)r * ECM_VERIFY_STRIPES * EC_METHOD_CHUNK_SIZE;
+    for (s0 = 0; s0 < nstripes && rc == 0; s0 += n) {
+        n = nstripes - s0 < ECM_VERIFY_STRIPES ? nstripes - s0 : ECM_VERIFY_STRIPES;
+        d.nstripes = n;
+        for (p = 0; p < d.k; p++)
+            d.in_base[p] = (const uint8_t *)in[p] + s0 * EC_METHOD_CHUNK_SIZE;
+        rc = ecc_combine(CTX(list)->isa, &d);
+        if (rc)
+            break;
+        for (t = 0; t < n; t++) {
+            flag = 0;
+            for (r = 0; r < nt; r++)
+                if (memcmp((const uint8_t *)d.out_base[r] + t * EC_METHOD_CHUNK_SIZE,
+                           (const uint8_t *)check[r] + (s0 + t) * EC_METHOD_CHUNK_SIZE,
+                           EC_METHOD_CHUNK_SIZE) != 0)
+                    flag |= 1u << bricks[r];
+            bad[s0 + t] = flag;
+            count += flag != 0;
+        }
+    }
+    free(scratch);
+    if (rc == 0 && nbad)
+        *nbad = count;
+    return rc;
+}
+
+static int32_t
+ecm_verify_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                       uintptr_t mask, const void *const *in, uintptr_t check_mask,
+                       const void *const *check, uint32_t *bad)
+{
+    ecd_combine_desc_t d;
+    uint32_t rows[ECM_MAX_K], nc = 0, nt = 0, p, r;
+    uint8_t bricks[ECM_MAX_N];
+    int rc;
+
+    rc = verify_args(list, mask, in, check_mask, check, bad, rows, bricks, &nc);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    /* device entry point: every buffer lives on `device` */
+    if (device < 0)
+        return -EINVAL;
+    for (p = 0; p < list->columns; p++)
+        if (!in[p] || ecd_ptr_device(in[p]) != device)
+            return -EINVAL;
+    for (r = 0; r < nc; r++)
+        if (!check[r] || ecd_ptr_device(check[r]) != device)
+            return -EINVAL;
+    if (ecd_ptr_device(bad) != device)
+        return -EINVAL;
+    if (!ecd_verify)
+        return -ENODEV;
+    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+    rc = heal_pattern(list, mask, rows, check_mask, d.pat, &nt);
+    if (rc)
+        return rc;
+    d.k = list->columns;
+    d.rows = nt;
+    d.nstripes = nstripes;
+    d.npatterns = 1;
+    d.pat_bytes = d.k + nt * d.k;
+    d.in_stride = EC_METHOD_CHUNK_SIZE;
+    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    for (p = 0; p < d.k; p++)
+        d.in_base[p] = in[p];
+    return ecd_verify(device, stream, &d, check, bricks, bad);
+}
+
 /* ------------------------------------------------- partial-stripe writes */
 
 static int32_t
@@ -2987,6 +3131,26 @@ ec_method_heal(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask, const 
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_heal", seq,
                    ecm_heal_impl(list, nstripes, mask, in, target_mask, out));
+}
+
+int32_t
+ec_method_verify(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask, const void *const *in,
+                 uintptr_t check_mask, const void *const *check, uint32_t *bad, uint64_t *nbad)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_verify", seq,
+                   ecm_verify_impl(list, nstripes, mask, in, check_mask, check, bad, nbad));
+}
+
+int32_t
+ec_method_verify_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                        uintptr_t mask, const void *const *in, uintptr_t check_mask,
+                        const void *const *check, uint32_t *bad)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_verify_device", seq,
+                   ecm_verify_device_impl(list, device, stream, nstripes, mask, in, check_mask,
+                                          check, bad));
 }
 
 int32_t

@@ -51,7 +51,7 @@ EXPORTS = (
     "ec_method_xover_observe_split",
     "ec_method_xover_observe_part",
     "ec_method_xover_observe", "ec_method_xover_reset", "ec_method_encode_rows",
-    "ec_method_encode_rows_device",
+    "ec_method_encode_rows_device", "ec_method_verify", "ec_method_verify_device",
 )
 
 
@@ -155,6 +155,8 @@ def _load():
         "ec_method_decode_batch": (i32, [P, u64, up, vp, vp, vp]),
         "ec_method_decode_mixed": (i32, [P, u64, u64, vp, vp, vp]),
         "ec_method_heal": (i32, [P, u64, up, vp, up, vp]),
+        "ec_method_verify": (i32, [P, u64, up, vp, up, vp, vp, ctypes.POINTER(u64)]),
+        "ec_method_verify_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
         "ec_method_encode_device": (i32, [P, ctypes.c_int, vp, u64, vp, vp]),
         "ec_method_decode_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_decode_mixed_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, u32, vp,
@@ -521,6 +523,17 @@ class ECMatrixList:
                                          _ptr_array(inp), target_mask, _ptr_array(out)),
                       "ec_method_heal")
 
+    def verify(self, nstripes, mask, inp, check_mask, check, bad):
+        """ec_method_verify: do the stored fragments `check` (bricks of
+        check_mask) agree with the k fragments `inp` (bricks of mask)?  `bad`
+        (uint32, one per stripe) gets bit i set where brick i's chunk differs;
+        returns the number of stripes with a non-zero flag."""
+        nbad = ctypes.c_uint64(0)
+        _check(lib.ec_method_verify(ctypes.byref(self._list), nstripes, mask, _ptr_array(inp),
+                                    check_mask, _ptr_array(check), addr(bad),
+                                    ctypes.byref(nbad)), "ec_method_verify")
+        return nbad.value
+
     # --- device-resident, asynchronous --------------------------------------
     def encode_rows_device(self, device, stream, nstripes, inp, row_mask, out):
         """ec_method_encode_rows_device: out[i] (None where the bit of
@@ -552,6 +565,14 @@ class ECMatrixList:
         return _check(lib.ec_method_heal_device(ctypes.byref(self._list), device, stream,
                                                 nstripes, mask, _ptr_array(inp), target_mask,
                                                 _ptr_array(out)), "ec_method_heal_device")
+
+    def verify_device(self, device, stream, nstripes, mask, inp, check_mask, check, bad):
+        """ec_method_verify_device: the same on device buffers (`bad` too),
+        queued on `stream`; the caller reduces `bad` itself."""
+        return _check(lib.ec_method_verify_device(ctypes.byref(self._list), device, stream,
+                                                  nstripes, mask, _ptr_array(inp), check_mask,
+                                                  _ptr_array(check), addr(bad)),
+                      "ec_method_verify_device")
 
 
 def sync_device(device, stream=None):

@@ -167,6 +167,40 @@ int32_t ec_method_heal(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask
                        const void *const *in, uintptr_t target_mask,
                        void *const *out);
 
+/* Consistency check: do the fragments of the bricks in check_mask agree with
+ * the k fragments in mask?  in[p] = fragment of the p-th set bit of mask,
+ * check[j] = stored fragment of the j-th set bit of check_mask (nstripes*512
+ * bytes each).  bad[t] (uint32, one per stripe) gets bit i set when brick i
+ * is in check_mask and its stored chunk of stripe t differs from the chunk
+ * the k fragments imply (E_i * inv(mask) applied to in[]); 0 = consistent.
+ * Every bad[0..nstripes) is written.  *nbad (may be NULL) = stripes with
+ * bad[t] != 0.  Nothing is decoded or regenerated to memory.
+ *
+ * The code is MDS, so one damaged chunk of a check brick sets that brick's
+ * bit alone, and one damaged chunk of a basis brick (mask) sets the bit of
+ * every check brick: to tell which basis brick it is, call again with
+ * another mask.  One mask per call.
+ *
+ * -EINVAL: mask is not exactly k bricks below n; check_mask is empty, has a
+ * bit at or above n or overlaps mask; a NULL pointer; bad not 4-byte
+ * aligned; host and device buffers mixed, or given to the wrong entry point.
+ * nstripes == 0 returns 0 and writes nothing.
+ *
+ * The host variant runs on the calling thread's CPU engine whatever the
+ * volume's engine is, and leaves ec_method_stats_t and the router alone.
+ * The device variant takes device pointers on `device` (bad[] included) and
+ * is asynchronous on `stream` like the calls below: matrices travel in the
+ * kernel arguments, each bad[t] is written by one plain store, nothing is
+ * pre-zeroed and nothing is counted on the device -- the caller reduces
+ * bad[] (4 bytes per (k + m) * 512 read). */
+int32_t ec_method_verify(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask,
+                         const void *const *in, uintptr_t check_mask,
+                         const void *const *check, uint32_t *bad, uint64_t *nbad);
+int32_t ec_method_verify_device(ec_matrix_list_t *list, int device, void *stream,
+                                uint64_t nstripes, uintptr_t mask, const void *const *in,
+                                uintptr_t check_mask, const void *const *check,
+                                uint32_t *bad);
+
 /* Partial-stripe write: the read-modify-write of
  * ec_writev_start (ec-inode-write.c:1987-2085) fused with ec_writev_encode.
  * The write's user data is the iovec list iov[0..count) (as the writev fop
