@@ -74,6 +74,15 @@ int ecd_combine(int device, void *stream, const ecd_combine_desc_t *d);
  * set where stripe t's stored chunk of row r differs from the prediction. */
 int ecd_verify(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                const uint8_t *check_brick, uint32_t *bad);
+/* Locating the damaged brick (ec_method_locate_device): d, check and
+ * check_brick as for ecd_verify, with d->rows >= 2; basis_brick[p] is the
+ * brick index of input p and ratio[(r - 1) * k + p] = G[r][p] / G[0][p] for
+ * the rows after the first (G = the coefficients in d->pat, none zero).
+ * loc[t] (device memory, one dword per stripe, all written) gets 0, the bit
+ * of the one brick that explains stripe t's mismatch, or bit 31 for none. */
+int ecd_locate(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
+               const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+               uint32_t *loc);
 int ecd_sync(int device, void *stream);
 
 /* ---- host-memory entry points: stripes are partitioned across `ndev`

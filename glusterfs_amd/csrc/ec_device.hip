@@ -1629,6 +1629,18 @@ int ecd_verify(int device, void *stream, const ecd_combine_desc_t *d, const void
     return ecdk_verify(pick_stream(stream), d, check, check_brick, bad);
 }
 
+int ecd_locate(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
+               const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+               uint32_t *loc)
+{
+    if (ecd_device_count() <= device || device < 0)
+        return -ENODEV;
+    DeviceGuard dg;
+    clear_stale_error();
+    HIPCHK(hipSetDevice(g_dev_ids[device]));
+    return ecdk_locate(pick_stream(stream), d, check, check_brick, basis_brick, ratio, loc);
+}
+
 int ecd_sync(int device, void *stream)
 {
     if (ecd_device_count() <= device || device < 0)

@@ -21,6 +21,10 @@ int ecdk_combine_host(hipStream_t s, const ecd_combine_desc_t *d);
 /* consistency check of ecd_verify (ec_verify_n) */
 int ecdk_verify(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, uint32_t *bad);
+/* the damaged brick per stripe of ecd_locate (ec_locate_n) */
+int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+                uint32_t *loc);
 /* Partial-stripe writes: materialise bytes [o0, o0+n) (n % 16 == 0) of the
  * virtual input {head[0:b1) | user[0:b2-b1) | tail[...]} into dst, and the
  * fused Vandermonde encode that reads interior stripes from user directly. */

@@ -16,6 +16,8 @@
  *            multiply by a jump into the searched XOR programs
  *   verify   the consistency check: ec_verify_n, the narrow tile with the
  *            check fragments staged beside the basis, 4 bytes out per stripe
+ *   locate   the damaged brick per stripe: ec_locate_n, verify's tile with
+ *            the syndromes kept in LDS and a second phase for dirty tiles
  *   stores   non-temporal on every device-path kernel except the 2+1 / 4+2
  *            register encoders (profiles/kbench_r01_nts.log)
  *   staging  LDS-DMA loads non-temporal for calls whose input exceeds the
@@ -945,6 +947,87 @@ int ecdk_verify(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
     /* the staging policy of ecdk_combine, by the bytes the call reads */
     const bool nt = nt_staging(a.nstripes * (a.k + a.rows) * ECD_CHUNK) && (o & 15u) == 0;
     return nt ? launch_verify_k<kLdsDmaNT>(s, a) : launch_verify_k<kLdsDmaDefault>(s, a);
+}
+
+/* ------------------------------------------- locating the damaged brick */
+
+namespace {
+
+template <int K, int NW, int LA>
+int launch_locate(hipStream_t s, const LocateArgs &a)
+{
+    const uint64_t g = (a.nstripes + 3) / 4;
+    if (g == 0)
+        return 0;
+    if (g > 0x7fffffffull)
+        return -EINVAL;
+    /* at most 31 inputs (ecdk_locate): 62 KiB + 32, under the 64 KiB a launch
+     * takes without raising the kernel's dynamic LDS limit */
+    const size_t lds = locate_n_lds(a.k + a.rows);
+    hipLaunchKernelGGL((ec_locate_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
+    return launch_ok("launch_locate");
+}
+
+/* the buckets and wave counts of launch_verify_k */
+template <int LA>
+int launch_locate_k(hipStream_t s, const LocateArgs &a)
+{
+    if (a.k <= 4)
+        return launch_locate<4, 4, LA>(s, a);
+    if (a.k <= 8)
+        return a.nstripes <= (1u << 17) ? launch_locate<8, 8, LA>(s, a)
+                                        : launch_locate<8, 4, LA>(s, a);
+    return launch_locate<16, 8, LA>(s, a);
+}
+
+} // namespace
+
+/* d, check, check_brick: as ecdk_verify, with at least two rows;
+ * basis_brick[p]: brick index of input p; ratio: (rows - 1) x k bytes,
+ * coefficient of row r over that of row 0; loc: nstripes device dwords. */
+int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+                uint32_t *loc)
+{
+    LocateArgs a;
+    if (d->k == 0 || d->k > ECD_MAX_K || d->rows < 2 || d->k + d->rows >= ECD_MAX_ROWS ||
+        d->npatterns != 1 || d->pat_ext || d->group_pattern ||
+        d->pat_bytes < d->k + d->rows * d->k || d->in_stride != ECD_CHUNK || !check ||
+        !check_brick || !basis_brick || !ratio || !loc || ((uintptr_t)loc & 3u))
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    a.k = d->k;
+    a.kw = (d->k + 3) / 4;
+    a.rows = d->rows;
+    a.nstripes = d->nstripes;
+    a.loc = loc;
+    if (a.kw * a.rows > kLocateWords)
+        return -EINVAL;
+    uintptr_t o = 0;
+    for (u32 p = 0; p < a.k; ++p) {
+        const uint8_t src = d->pat[p];
+        if (src >= ECD_MAX_ROWS || !d->in_base[src] || basis_brick[p] >= 31)
+            return -EINVAL;
+        a.in[p] = static_cast<const uint8_t *>(d->in_base[src]);
+        o |= (uintptr_t)a.in[p];
+        a.bbrick[p >> 2] |= (u32)basis_brick[p] << ((p & 3u) * 8u);
+    }
+    for (u32 r = 0; r < a.rows; ++r) {
+        if (!check[r] || check_brick[r] >= 31)
+            return -EINVAL;
+        a.in[a.k + r] = static_cast<const uint8_t *>(check[r]);
+        o |= (uintptr_t)check[r];
+        a.cbrick[r >> 2] |= (u32)check_brick[r] << ((r & 3u) * 8u);
+        for (u32 p = 0; p < a.k; ++p) {
+            a.coef[r * a.kw + (p >> 2)] |= (u32)d->pat[a.k + r * a.k + p] << ((p & 3u) * 8u);
+            if (r > 0)
+                a.ratio[(r - 1) * a.kw + (p >> 2)] |= (u32)ratio[(r - 1) * a.k + p]
+                                                      << ((p & 3u) * 8u);
+        }
+    }
+    /* the staging policy of ecdk_verify, by the bytes the call reads */
+    const bool nt = nt_staging(a.nstripes * (a.k + a.rows) * ECD_CHUNK) && (o & 15u) == 0;
+    return nt ? launch_locate_k<kLdsDmaNT>(s, a) : launch_locate_k<kLdsDmaDefault>(s, a);
 }
 
 /* Host-buffer combines with k <= 8 run the persistent double-buffered

@@ -1566,6 +1566,157 @@ constexpr size_t verify_n_lds(u32 inputs)
     return (size_t)inputs * 4 * ECD_CHUNK + 4 * sizeof(u32);
 }
 
+/* ------------------------------------------- locating the damaged brick */
+
+constexpr u32 kLocateMany = 0x80000000u;      /* EC_MI355X_LOCATE_MANY */
+constexpr u32 kLocateWords = ECD_MAX_K / 4 * (ECD_MAX_ROWS / 2); /* 16 rows of 4 words */
+
+/* Kernel arguments of ec_locate_n: VerifyArgs' input list and coefficient
+ * rows, the ratios q[r][p] = G[r][p] / G[0][p] of rows 1 .. rows-1 laid out
+ * like the coefficients (row r at word (r - 1) * kw), and the brick index of
+ * every basis input and every check row, a byte each. */
+struct LocateArgs {
+    const uint8_t *in[ECD_MAX_ROWS];
+    u32 *loc;
+    uint64_t nstripes;
+    u32 k, kw, rows, pad;
+    u32 bbrick[ECD_MAX_K / 4];
+    u32 cbrick[ECD_MAX_ROWS / 4];
+    u32 coef[kLocateWords];
+    u32 ratio[kLocateWords];
+};
+
+/* ec_method_locate_device: which brick's chunk is wrong?  Phase 1 is
+ * ec_verify_n (the same tile, staging and row spread) except that the lane
+ * keeps the syndrome -- prediction ^ stored, 8 words -- in the check chunk's
+ * own LDS slot (it owns that dword column and no other row reads the slot),
+ * and the stripe's flag collects the brick bits of its non-zero rows.  A tile
+ * whose four flags are zero stores four zeros and is done: the normal case,
+ * at verify's cost plus the write-back.  The decision is read from LDS after
+ * a barrier, so the whole block takes it together.
+ *
+ * Phase 2, for a tile with a dirty stripe.  A flag of one bit is that check
+ * brick.  With two or more, an error e in basis input p alone would give
+ * s_r = G[r][p] * e for every row, i.e. s_r = q[r][p] * s_0: the basis
+ * positions are spread over the waves, each tests that equality for rows
+ * 1 .. rows-1 over its dword column, the 16 lanes of a stripe vote, and a
+ * position that passes ORs its brick bit into the stripe's result word (at
+ * most one can pass: two would make the stripe consistent).  No barrier sits
+ * in a loop, so waves without a row or a position reach every one.  Each
+ * loc[t] leaves by one plain dword store. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_locate_n(const LocateArgs a)
+{
+    constexpr u32 T = 4;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 tid = threadIdx.x;
+    const u32 k = a.k, ni = a.k + a.rows;
+    const uint64_t t0 = (uint64_t)blockIdx.x * T;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    /* flags[s]: brick bits of stripe s's non-zero rows; flags[T + s]: the
+     * brick bit of the basis position that explains them */
+    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
+    if (tid < 2 * T)
+        flags[tid] = 0;
+    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        return a.in[p] + st * ECD_CHUNK;
+    }, ni, t0, a.nstripes, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    uint8_t *col = lds + cs * 64u + cc * 4u;
+    const bool live = t0 + cs < a.nstripes;
+    for (u32 r = wave; r < a.rows; r += NW) {
+        const u32 rw = a.kw * r;
+        const u32 w0 = a.coef[rw];
+        const u32 w1 = K > 4 ? a.coef[rw + 1] : 0u;
+        const u32 w2 = K > 8 ? a.coef[rw + 2] : 0u;
+        const u32 w3 = K > 12 ? a.coef[rw + 3] : 0u;
+        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
+        u32 acc[8][1], y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            acc[b][0] = 0;
+#pragma unroll 1
+        for (u32 p = 0; p < k; ++p) {
+            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+            cl = (cl >> 8) | (ch << 56);
+            ch >>= 8;
+            if (c == 0)
+                continue;
+            const uint8_t *src = col + p * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+            ecgf::mul_xor_jt<1>(c, acc, y);
+        }
+        /* the syndrome replaces the stored chunk in LDS */
+        uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
+        u32 d = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (T * 64u));
+            const u32 s = acc[b][0] ^ *w;
+            *w = s;
+            d |= s;
+        }
+        const uint64_t vote = __ballot(live && d != 0);
+        const u32 brick = __builtin_amdgcn_readfirstlane((a.cbrick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
+        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
+            atomicOr(&flags[cs], 1u << brick);
+    }
+    __syncthreads();
+    const u32 any = __builtin_amdgcn_readfirstlane(flags[0] | flags[1] | flags[2] | flags[3]);
+    if (any == 0) {
+        if (tid < T && t0 + tid < a.nstripes)
+            a.loc[t0 + tid] = 0;
+        return;
+    }
+    /* a stripe with two or more non-zero rows looks for its basis position
+     * (stripes past nstripes have no flag) */
+    const u32 mine = flags[cs];
+    const bool open = (mine & (mine - 1u)) != 0;
+    const uint8_t *s0 = col + k * (T * ECD_CHUNK);
+    for (u32 p = wave; p < k; p += NW) {
+        u32 y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            y[b][0] = *reinterpret_cast<const u32 *>(s0 + (u32)b * (T * 64u));
+        u32 d = 0;
+#pragma unroll 1
+        for (u32 r = 1; r < a.rows; ++r) {
+            const u32 q = __builtin_amdgcn_readfirstlane(
+                (a.ratio[(r - 1) * a.kw + (p >> 2)] >> ((p & 3u) * 8u)) & 0xFFu);
+            u32 acc[8][1];
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                acc[b][0] = 0;
+            if (q != 0)
+                ecgf::mul_xor_jt<1>(q, acc, y);
+            const uint8_t *sr = col + (k + r) * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
+        }
+        const uint64_t vote = __ballot(d != 0);
+        const u32 brick = __builtin_amdgcn_readfirstlane((a.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
+        if (cc == 0 && open && ((vote >> (cs * 16u)) & 0xFFFFu) == 0)
+            atomicOr(&flags[T + cs], 1u << brick);
+    }
+    __syncthreads();
+    if (tid < T && t0 + tid < a.nstripes) {
+        const u32 f = flags[tid], b = flags[T + tid];
+        a.loc[t0 + tid] = (f & (f - 1u)) == 0 ? f : b ? b : kLocateMany;
+    }
+}
+
+/* dynamic LDS of an ec_locate_n launch: the tile and two words per stripe */
+constexpr size_t locate_n_lds(u32 inputs)
+{
+    return (size_t)inputs * 4 * ECD_CHUNK + 8 * sizeof(u32);
+}
+
 /* Zero-copy variant for the host-buffer path, where every input and output
  * lives in pinned host memory and the CUs read and write it over PCIe
  * (ec_device.hip run_pipeline).  There the link, not HBM or the VALU, is the

@@ -2781,6 +2781,259 @@ ecm_verify_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_
     return ecd_verify(device, stream, &d, check, bricks, bad);
 }
 
+/* ------------------------------------------- locating the damaged brick */
+
+/* Weak like ecd_verify: without the symbol ec_method_locate_device is
+ * -ENODEV. */
+extern __typeof__(ecd_locate) ecd_locate __attribute__((weak));
+
+/* What both entry points derive from avail_mask: the basis B (its k lowest
+ * bricks; rows[] = their matrix rows, bb[] = their indices), the check set R
+ * (the other nr = a - k >= 2 bricks, cb[]), and the pointer lists in that
+ * order. */
+typedef struct {
+    uintptr_t bmask, rmask;
+    uint32_t rows[ECM_MAX_K], nr;
+    uint8_t bb[ECM_MAX_K], cb[ECM_MAX_N];
+    const void *in[ECM_MAX_K];
+    const void *check[ECM_MAX_N];
+} ecm_locate_sets_t;
+
+static int
+locate_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags,
+            const uint32_t *loc, ecm_locate_sets_t *s)
+{
+    uint32_t i, nb = 0, nr = 0;
+
+    if (!list || !CTX(list) || !frags || !loc || ((uintptr_t)loc & 3u))
+        return -EINVAL;
+    if ((avail_mask >> list->rows) != 0 || popcount_mask(avail_mask) < list->columns + 2)
+        return -EINVAL;
+    s->bmask = s->rmask = 0;
+    for (i = 0; i < list->rows; i++) {
+        if (!((avail_mask >> i) & 1))
+            continue;
+        if (!frags[i])
+            return -EINVAL;
+        if (nb < list->columns) {
+            s->bmask |= (uintptr_t)1 << i;
+            s->bb[nb] = (uint8_t)i;
+            s->in[nb++] = frags[i];
+        } else {
+            s->rmask |= (uintptr_t)1 << i;
+            s->cb[nr] = (uint8_t)i;
+            s->check[nr++] = frags[i];
+        }
+    }
+    s->nr = nr;
+    rows_from_mask(s->bmask, s->rows);
+    return mask_rows_ok(list, s->bmask, s->rows) ? 0 : -EINVAL;
+}
+
+/* The prediction matrix G (nr x k, in d->pat after its k source bytes) and
+ * the ratios q[c][b] = G[c][b] / G[c0][b] of the rows after the first, (nr -
+ * 1) x k.  The code is MDS, so no entry of G is zero. */
+static int
+locate_tables(ec_matrix_list_t *list, const ecm_locate_sets_t *s, ecd_combine_desc_t *d,
+              uint8_t *ratio)
+{
+    const uint32_t k = list->columns;
+    uint32_t nt = 0, r, p, q;
+    int rc;
+
+    memset(d, 0, offsetof(ecd_combine_desc_t, pat));
+    rc = heal_pattern(list, s->bmask, s->rows, s->rmask, d->pat, &nt);
+    if (rc)
+        return rc;
+    if (nt != s->nr)
+        return -EINVAL;
+    for (r = 1; r < nt; r++)
+        for (p = 0; p < k; p++) {
+            q = ec_method_gf_div(d->pat[k + r * k + p], d->pat[k + p]);
+            if (q == 0 || q >= EC_GF_SIZE)
+                return -EINVAL;
+            ratio[(r - 1) * k + p] = (uint8_t)q;
+        }
+    d->k = k;
+    d->rows = nt;
+    d->npatterns = 1;
+    d->pat_bytes = k + nt * k;
+    d->in_stride = EC_METHOD_CHUNK_SIZE;
+    d->out_stride = EC_METHOD_CHUNK_SIZE;
+    return 0;
+}
+
+static int
+chunk_is_zero(const uint8_t *c)
+{
+    uint64_t w, acc = 0;
+    uint32_t i;
+
+    for (i = 0; i < EC_METHOD_CHUNK_SIZE; i += 8) {
+        memcpy(&w, c + i, 8);
+        acc |= w;
+    }
+    return acc == 0;
+}
+
+/* The rare path of the host variant: one stripe whose syndromes syn[r] (nr
+ * chunks, 512 bytes apart) are not all zero.  The rule of ec_method.h: one
+ * non-zero syndrome is that check brick; otherwise the basis brick b with
+ * syn[r] == q[r][b] * syn[0] for every r > 0, or MANY. */
+static int
+locate_classify(int isa, const ecm_locate_sets_t *s, uint32_t k, const uint8_t *ratio,
+                const uint8_t *syn, uint32_t *out)
+{
+    ecd_combine_desc_t m;
+    uint8_t prod[EC_METHOD_CHUNK_SIZE] __attribute__((aligned(64)));
+    uint32_t r, b, nz = 0, last = 0;
+    int rc;
+
+    for (r = 0; r < s->nr; r++)
+        if (!chunk_is_zero(syn + (size_t)r * EC_METHOD_CHUNK_SIZE)) {
+            nz++;
+            last = r;
+        }
+    if (nz == 0) {
+        *out = 0;
+        return 0;
+    }
+    if (nz == 1) {
+        *out = 1u << s->cb[last];
+        return 0;
+    }
+    *out = EC_MI355X_LOCATE_MANY;
+    memset(&m, 0, offsetof(ecd_combine_desc_t, pat));
+    m.k = 1;
+    m.rows = 1;
+    m.nstripes = 1;
+    m.npatterns = 1;
+    m.pat_bytes = 2;
+    m.in_stride = EC_METHOD_CHUNK_SIZE;
+    m.out_stride = EC_METHOD_CHUNK_SIZE;
+    m.in_base[0] = syn;
+    m.out_base[0] = prod;
+    m.pat[0] = 0;
+    for (b = 0; b < k; b++) {
+        for (r = 1; r < s->nr; r++) {
+            m.pat[1] = ratio[(r - 1) * k + b];
+            rc = ecc_combine(isa, &m);
+            if (rc)
+                return rc;
+            if (memcmp(prod, syn + (size_t)r * EC_METHOD_CHUNK_SIZE, EC_METHOD_CHUNK_SIZE) != 0)
+                break;
+        }
+        if (r == s->nr) {
+            *out = 1u << s->bb[b];
+            return 0;
+        }
+    }
+    return 0;
+}
+
+static int32_t
+ecm_locate_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                const void *const *frags, uint32_t *loc, uint64_t *nbad)
+{
+    ecm_locate_sets_t s;
+    ecd_combine_desc_t d;
+    uint8_t ratio[ECM_MAX_N * ECM_MAX_K];
+    uint8_t syn[ECM_MAX_N * EC_METHOD_CHUNK_SIZE] __attribute__((aligned(64)));
+    uint32_t p, r, k, dirty;
+    uint64_t s0, t, n, count = 0;
+    uint8_t *scratch;
+    int rc;
+
+    rc = locate_args(list, avail_mask, frags, loc, &s);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    k = list->columns;
+    /* host entry point: device buffers go to _device */
+    if (!bufs_on(s.in, k, -1) || !bufs_on(s.check, s.nr, -1) || ecd_ptr_device(loc) >= 0)
+        return -EINVAL;
+    rc = locate_tables(list, &s, &d, ratio);
+    if (rc)
+        return rc;
+    /* as ecm_verify_impl: the CPU engine predicts a few dozen stripes of the
+     * check bricks; a stripe with a mismatch then takes the slow path */
+    scratch = (uint8_t *)malloc((size_t)ECM_VERIFY_STRIPES * s.nr * EC_METHOD_CHUNK_SIZE);
+    if (!scratch)
+        return -ENOMEM;
+    for (r = 0; r < s.nr; r++)
+        d.out_base[r] = scratch + (size_t)r * ECM_VERIFY_STRIPES * EC_METHOD_CHUNK_SIZE;
+    for (s0 = 0; s0 < nstripes && rc == 0; s0 += n) {
+        n = nstripes - s0 < ECM_VERIFY_STRIPES ? nstripes - s0 : ECM_VERIFY_STRIPES;
+        d.nstripes = n;
+        for (p = 0; p < k; p++)
+            d.in_base[p] = (const uint8_t *)s.in[p] + s0 * EC_METHOD_CHUNK_SIZE;
+        rc = ecc_combine(CTX(list)->isa, &d);
+        if (rc)
+            break;
+        for (t = 0; t < n && rc == 0; t++) {
+            dirty = 0;
+            for (r = 0; r < s.nr; r++)
+                dirty |= memcmp((const uint8_t *)d.out_base[r] + t * EC_METHOD_CHUNK_SIZE,
+                                (const uint8_t *)s.check[r] + (s0 + t) * EC_METHOD_CHUNK_SIZE,
+                                EC_METHOD_CHUNK_SIZE) != 0;
+            if (!dirty) {
+                loc[s0 + t] = 0;
+                continue;
+            }
+            for (r = 0; r < s.nr; r++) {
+                const uint8_t *pr = (const uint8_t *)d.out_base[r] + t * EC_METHOD_CHUNK_SIZE;
+                const uint8_t *st = (const uint8_t *)s.check[r] + (s0 + t) * EC_METHOD_CHUNK_SIZE;
+                for (p = 0; p < EC_METHOD_CHUNK_SIZE; p++)
+                    syn[r * EC_METHOD_CHUNK_SIZE + p] = pr[p] ^ st[p];
+            }
+            rc = locate_classify(CTX(list)->isa, &s, k, ratio, syn, &loc[s0 + t]);
+            count++;
+        }
+    }
+    free(scratch);
+    if (rc == 0 && nbad)
+        *nbad = count;
+    return rc;
+}
+
+static int32_t
+ecm_locate_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                       uintptr_t avail_mask, const void *const *frags, uint32_t *loc)
+{
+    ecm_locate_sets_t s;
+    ecd_combine_desc_t d;
+    uint8_t ratio[ECM_MAX_N * ECM_MAX_K];
+    uint32_t p;
+    int rc;
+
+    rc = locate_args(list, avail_mask, frags, loc, &s);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    /* device entry point: every buffer lives on `device` */
+    if (device < 0)
+        return -EINVAL;
+    for (p = 0; p < list->columns; p++)
+        if (ecd_ptr_device(s.in[p]) != device)
+            return -EINVAL;
+    for (p = 0; p < s.nr; p++)
+        if (ecd_ptr_device(s.check[p]) != device)
+            return -EINVAL;
+    if (ecd_ptr_device(loc) != device)
+        return -EINVAL;
+    if (!ecd_locate)
+        return -ENODEV;
+    rc = locate_tables(list, &s, &d, ratio);
+    if (rc)
+        return rc;
+    d.nstripes = nstripes;
+    for (p = 0; p < d.k; p++)
+        d.in_base[p] = s.in[p];
+    return ecd_locate(device, stream, &d, s.check, s.cb, s.bb, ratio, loc);
+}
+
 /* ------------------------------------------------- partial-stripe writes */
 
 static int32_t
@@ -3151,6 +3404,25 @@ ec_method_verify_device(ec_matrix_list_t *list, int device, void *stream, uint64
     return ecm_ret("ec_method_verify_device", seq,
                    ecm_verify_device_impl(list, device, stream, nstripes, mask, in, check_mask,
                                           check, bad));
+}
+
+int32_t
+ec_method_locate(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                 const void *const *frags, uint32_t *loc, uint64_t *nbad)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_locate", seq,
+                   ecm_locate_impl(list, nstripes, avail_mask, frags, loc, nbad));
+}
+
+int32_t
+ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                        uintptr_t avail_mask, const void *const *frags, uint32_t *loc)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_locate_device", seq,
+                   ecm_locate_device_impl(list, device, stream, nstripes, avail_mask, frags,
+                                          loc));
 }
 
 int32_t

@@ -27,6 +27,7 @@ EC_METHOD_MAX_FRAGMENTS = 16
 EC_METHOD_WORD_SIZE = 64
 EC_METHOD_CHUNK_SIZE = EC_METHOD_WORD_SIZE * EC_GF_BITS
 EC_MAX_NODES = 31
+EC_MI355X_LOCATE_MANY = 0x80000000
 
 # Every symbol include/ec_method.h declares (checked by tests/test_abi.py).
 EXPORTS = (
@@ -52,6 +53,7 @@ EXPORTS = (
     "ec_method_xover_observe_part",
     "ec_method_xover_observe", "ec_method_xover_reset", "ec_method_encode_rows",
     "ec_method_encode_rows_device", "ec_method_verify", "ec_method_verify_device",
+    "ec_method_locate", "ec_method_locate_device",
 )
 
 
@@ -157,6 +159,8 @@ def _load():
         "ec_method_heal": (i32, [P, u64, up, vp, up, vp]),
         "ec_method_verify": (i32, [P, u64, up, vp, up, vp, vp, ctypes.POINTER(u64)]),
         "ec_method_verify_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
+        "ec_method_locate": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64)]),
+        "ec_method_locate_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_encode_device": (i32, [P, ctypes.c_int, vp, u64, vp, vp]),
         "ec_method_decode_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_decode_mixed_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, u32, vp,
@@ -534,6 +538,17 @@ class ECMatrixList:
                                     ctypes.byref(nbad)), "ec_method_verify")
         return nbad.value
 
+    def locate(self, nstripes, avail_mask, frags, loc):
+        """ec_method_locate: which brick's chunk is wrong?  `frags` is indexed
+        by brick (None outside avail_mask, which needs k + 2 bricks); `loc`
+        (uint32, one per stripe) gets 0, 1 << brick or EC_MI355X_LOCATE_MANY; returns
+        the number of stripes with a non-zero entry."""
+        nbad = ctypes.c_uint64(0)
+        _check(lib.ec_method_locate(ctypes.byref(self._list), nstripes, avail_mask,
+                                    _ptr_array(frags), addr(loc), ctypes.byref(nbad)),
+               "ec_method_locate")
+        return nbad.value
+
     # --- device-resident, asynchronous --------------------------------------
     def encode_rows_device(self, device, stream, nstripes, inp, row_mask, out):
         """ec_method_encode_rows_device: out[i] (None where the bit of
@@ -573,6 +588,13 @@ class ECMatrixList:
                                                   nstripes, mask, _ptr_array(inp), check_mask,
                                                   _ptr_array(check), addr(bad)),
                       "ec_method_verify_device")
+
+    def locate_device(self, device, stream, nstripes, avail_mask, frags, loc):
+        """ec_method_locate_device: the same on device buffers (`loc` too),
+        queued on `stream`."""
+        return _check(lib.ec_method_locate_device(ctypes.byref(self._list), device, stream,
+                                                  nstripes, avail_mask, _ptr_array(frags),
+                                                  addr(loc)), "ec_method_locate_device")
 
 
 def sync_device(device, stream=None):

@@ -179,7 +179,7 @@ int32_t ec_method_heal(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask
  * The code is MDS, so one damaged chunk of a check brick sets that brick's
  * bit alone, and one damaged chunk of a basis brick (mask) sets the bit of
  * every check brick: to tell which basis brick it is, call again with
- * another mask.  One mask per call.
+ * another mask (or ec_method_locate below, in one pass).  One mask per call.
  *
  * -EINVAL: mask is not exactly k bricks below n; check_mask is empty, has a
  * bit at or above n or overlaps mask; a NULL pointer; bad not 4-byte
@@ -200,6 +200,49 @@ int32_t ec_method_verify_device(ec_matrix_list_t *list, int device, void *stream
                                 uint64_t nstripes, uintptr_t mask, const void *const *in,
                                 uintptr_t check_mask, const void *const *check,
                                 uint32_t *bad);
+
+/* Locating the damaged brick: one pass over the stored fragments that names,
+ * per stripe, the brick whose chunk is wrong, so that ec_method_heal can be
+ * given a mask without it.  frags[0..n) is indexed by brick as in
+ * ec_method_decode_mixed (nstripes*512 bytes each); entries of bricks outside
+ * avail_mask are not read and may be NULL.  avail_mask names the a >= k + 2
+ * bricks whose stored fragments are at hand.  loc[t] (uint32, one per stripe,
+ * every loc[0..nstripes) written) is
+ *   0                       the a chunks of stripe t are mutually consistent
+ *                           (any k of them imply the others);
+ *   1u << i                 they are not, and brick i of avail_mask is the one
+ *                           brick whose removal leaves the other a - 1 chunks
+ *                           mutually consistent;
+ *   EC_MI355X_LOCATE_MANY   they are not, and no single brick explains it.
+ * With a >= k + 2 at most one brick can qualify (two would give two codewords
+ * that agree on a - 2 >= k positions, hence one codeword), so exactly one of
+ * the three holds.  *nbad (host variant, may be NULL) = stripes with
+ * loc[t] != 0.
+ *
+ * What the code can promise: one damaged chunk per stripe is always named
+ * correctly.  With a - k >= 3, two damaged chunks in a stripe are always
+ * MANY (distance >= 4).  With a - k == 2 two damaged chunks can imitate a
+ * single error in a third brick: the code then has distance 3, so this is a
+ * property of the code, not of the call.
+ *
+ * -EINVAL: a NULL list, frags or loc; loc not 4-byte aligned; a bit of
+ * avail_mask at or above n; fewer than k + 2 bits (so every call on a 2+1
+ * volume); a NULL frags[i] for a set bit; host and device buffers mixed, or
+ * given to the wrong entry point (the device variant wants every buffer, loc
+ * included, on `device`).  nstripes == 0 returns 0 after these checks and
+ * writes nothing.  One avail_mask per call.
+ *
+ * Like ec_method_verify, the host variant runs on the calling thread's CPU
+ * engine whatever the volume's engine is and leaves ec_method_stats_t, the
+ * router and the run-time compiler alone; the device variant is asynchronous
+ * on `stream`, pre-zeroes nothing, uses no global atomics and writes each
+ * loc[t] by one plain store (-ENODEV where the device layer lacks it). */
+#define EC_MI355X_LOCATE_MANY 0x80000000u /* bit 31: EC_MI355X_MAX_NODES is 31 */
+int32_t ec_method_locate(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                         const void *const *frags, uint32_t *loc, uint64_t *nbad);
+int32_t ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream,
+                                uint64_t nstripes, uintptr_t avail_mask,
+                                const void *const *frags, uint32_t *loc);
 
 /* Partial-stripe write: the read-modify-write of
  * ec_writev_start (ec-inode-write.c:1987-2085) fused with ec_writev_encode.
