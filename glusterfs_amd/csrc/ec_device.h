@@ -83,6 +83,16 @@ int ecd_verify(int device, void *stream, const ecd_combine_desc_t *d, const void
 int ecd_locate(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                uint32_t *loc);
+/* Repairing what locate named (ec_method_repair_device): frags[] is indexed
+ * by brick and read for the bits of avail (no bit at or above 31); bset is
+ * the k + 1 lowest bricks of avail, ascending: the basis B of ecd_locate and
+ * c0; coef[i * k + p], for every brick i of avail, is the coefficient of
+ * input p of B_i, the k lowest bricks of avail other than i.  Where loc[t]
+ * (device memory, read only) is 1 << i for a brick i of avail, chunk t of
+ * frags[i] is overwritten with the prediction from B_i; any other value
+ * leaves stripe t alone. */
+int ecd_repair(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
+               uint32_t avail, const uint8_t *bset, const uint8_t *coef, const uint32_t *loc);
 int ecd_sync(int device, void *stream);
 
 /* ---- host-memory entry points: stripes are partitioned across `ndev`

@@ -25,6 +25,9 @@ int ecdk_verify(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
 int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                 uint32_t *loc);
+/* rewriting the chunks loc[] names, of ecd_repair (ec_repair_n) */
+int ecdk_repair(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
+                const uint8_t *bset, const uint8_t *coef, const uint32_t *loc);
 /* Partial-stripe writes: materialise bytes [o0, o0+n) (n % 16 == 0) of the
  * virtual input {head[0:b1) | user[0:b2-b1) | tail[...]} into dst, and the
  * fused Vandermonde encode that reads interior stripes from user directly. */

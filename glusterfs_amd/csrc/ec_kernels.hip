@@ -18,6 +18,8 @@
  *            check fragments staged beside the basis, 4 bytes out per stripe
  *   locate   the damaged brick per stripe: ec_locate_n, verify's tile with
  *            the syndromes kept in LDS and a second phase for dirty tiles
+ *   repair   the chunks locate named: ec_repair_n, a ballot scan of loc[]
+ *            and up to four dirty stripes of one brick per wave, no LDS
  *   stores   non-temporal on every device-path kernel except the 2+1 / 4+2
  *            register encoders (profiles/kbench_r01_nts.log)
  *   staging  LDS-DMA loads non-temporal for calls whose input exceeds the
@@ -1028,6 +1030,56 @@ int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
     /* the staging policy of ecdk_verify, by the bytes the call reads */
     const bool nt = nt_staging(a.nstripes * (a.k + a.rows) * ECD_CHUNK) && (o & 15u) == 0;
     return nt ? launch_locate_k<kLdsDmaNT>(s, a) : launch_locate_k<kLdsDmaDefault>(s, a);
+}
+
+/* ------------------------------------------- repairing the named chunks */
+
+static int cu_count();
+
+/* k, nstripes: the geometry; frags: by brick, read for the bits of avail;
+ * bset: the k + 1 brick indices of the basis and c0, ascending; coef[i * k +
+ * p]: coefficient of input p of B_i for every brick i of avail; loc: nstripes
+ * device dwords, read only. */
+int ecdk_repair(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
+                const uint8_t *bset, const uint8_t *coef, const uint32_t *loc)
+{
+    RepairArgs a;
+    if (k == 0 || k > ECD_MAX_K || !frags || !bset || !coef || !loc || ((uintptr_t)loc & 3u) ||
+        (avail >> 31) != 0)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    a.k = k;
+    a.avail = avail;
+    a.nstripes = nstripes;
+    a.loc = loc;
+    /* bset is the k + 1 lowest bricks of avail in ascending order */
+    u32 rest = avail;
+    for (u32 p = 0; p <= k; ++p) {
+        if (rest == 0 || bset[p] != (u32)__builtin_ctz(rest))
+            return -EINVAL;
+        rest &= rest - 1u;
+        if (p < k)
+            a.bmask |= 1u << bset[p];
+        a.bset[p >> 2] |= (u32)bset[p] << ((p & 3u) * 8u);
+    }
+    for (u32 i = 0; i < 31; ++i) {
+        if (!((avail >> i) & 1u))
+            continue;
+        if (!frags[i])
+            return -EINVAL;
+        a.frag[i] = static_cast<uint8_t *>(frags[i]);
+        for (u32 p = 0; p < k; ++p)
+            a.coef[i][p >> 2] |= (u32)coef[i * k + p] << ((p & 3u) * 8u);
+    }
+    if (nstripes == 0)
+        return 0;
+    /* one lane per loc word; a few blocks per CU stride over the rest */
+    uint64_t g = (nstripes + kRepairThreads - 1) / kRepairThreads;
+    const uint64_t cap = (uint64_t)cu_count() * 8u;
+    if (g > cap)
+        g = cap;
+    hipLaunchKernelGGL(ec_repair_n, dim3((u32)g), dim3(kRepairThreads), 0, s, a);
+    return launch_ok("launch_repair");
 }
 
 /* Host-buffer combines with k <= 8 run the persistent double-buffered

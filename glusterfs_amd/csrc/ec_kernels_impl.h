@@ -1717,6 +1717,106 @@ constexpr size_t locate_n_lds(u32 inputs)
     return (size_t)inputs * 4 * ECD_CHUNK + 8 * sizeof(u32);
 }
 
+/* ------------------------------------------- repairing the named chunks */
+
+/* Kernel arguments of ec_repair_n.  frag[] is indexed by brick (null outside
+ * avail); bset holds the brick bytes of locate's basis B (the k lowest bricks
+ * of avail, ascending) followed by c0, the first brick after B; bmask is B as
+ * a mask.  coef[i] is the row of k coefficients that predicts brick i from
+ * B_i, the k lowest bricks of avail other than i: B itself when i is not in
+ * B, else B without i and with c0 appended (still ascending, c0 > B). */
+struct RepairArgs {
+    uint8_t *frag[ECD_MAX_ROWS];
+    const u32 *loc;
+    uint64_t nstripes;
+    u32 k, avail, bmask, pad;
+    u32 bset[ECD_MAX_K / 4 + 2];
+    u32 coef[ECD_MAX_ROWS][ECD_MAX_K / 4];
+};
+
+constexpr u32 kRepairThreads = 256;
+
+/* ec_method_repair_device: rewrite the chunks loc[] names.  The work is
+ * sparse, so there is no tile: the grid strides over loc[], each lane of a
+ * wave reads one word and the ballot of "one bit, of a brick in avail" is
+ * the wave's dirty set, empty in the normal case.  The jump-table multiply
+ * wants a wave-uniform coefficient, so the wave takes the brick of its first
+ * dirty lane and up to four dirty stripes of its 64 that name that brick: 16
+ * lanes per stripe, each lane one dword column of the 8 planes (the layout of
+ * ec_locate_n), straight from global memory at byte addresses (gfx950 runs in
+ * unaligned access mode, see load_plane_unaligned).  It clears those bits and
+ * loops until the set is empty.  Every stripe belongs to one wave, and the
+ * named chunk is written and never read (B_i excludes i): no LDS, no barrier,
+ * no atomics.  Every branch around the multiply is wave-uniform; only the
+ * loads and stores are predicated by `live`. */
+__global__ __launch_bounds__(kRepairThreads) void ec_repair_n(const RepairArgs a)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const u32 grp = lane >> 4, cc = lane & 15u;
+    const u32 k = a.k;
+    const uint64_t step = (uint64_t)gridDim.x * kRepairThreads;
+    for (uint64_t base = ((uint64_t)blockIdx.x * (kRepairThreads / 64u) + wave) * 64u;
+         base < a.nstripes; base += step) {
+        const uint64_t t = base + lane;
+        const u32 w = t < a.nstripes ? a.loc[t] : 0u;
+        /* MANY is bit 31 and avail has no bit at or above n <= 31 */
+        uint64_t dirty = __ballot(w != 0 && (w & (w - 1u)) == 0 && (w & a.avail) != 0);
+        while (dirty != 0) {
+            const u32 first = __builtin_amdgcn_readfirstlane((u32)__builtin_ctzll(dirty));
+            const u32 wf = __builtin_amdgcn_readlane(w, first);
+            const u32 brick = __builtin_amdgcn_readfirstlane((u32)__builtin_ctz(wf));
+            /* up to four stripes of the set that name this brick */
+            const uint64_t same = __ballot(w == wf) & dirty;
+            uint64_t rest = same;
+            u32 sel[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                sel[g] = rest ? (u32)__builtin_ctzll(rest) : 64u;
+                rest &= rest - 1u;
+            }
+            dirty &= ~(same ^ rest);
+            const u32 src = grp == 0 ? sel[0] : grp == 1 ? sel[1] : grp == 2 ? sel[2] : sel[3];
+            const bool live = src < 64u;
+            const uint64_t off = (base + src) * ECD_CHUNK + cc * 4u;
+            /* position of the brick in B (k: a check brick); input p of B_i
+             * is entry p of bset, skipping that position */
+            const u32 j = (a.bmask >> brick) & 1u ? (u32)__builtin_popcount(a.bmask & ((1u << brick) - 1u))
+                                                  : k;
+            uint64_t cl = (uint64_t)a.coef[brick][0] | ((uint64_t)a.coef[brick][1] << 32);
+            uint64_t ch = (uint64_t)a.coef[brick][2] | ((uint64_t)a.coef[brick][3] << 32);
+            u32 acc[8][1], y[8][1];
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                acc[b][0] = 0;
+#pragma unroll 1
+            for (u32 p = 0; p < k; ++p) {
+                const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+                cl = (cl >> 8) | (ch << 56);
+                ch >>= 8;
+                const u32 q = p + (p >= j ? 1u : 0u);
+                const u32 sb = __builtin_amdgcn_readfirstlane((a.bset[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu);
+                const uint8_t *in = a.frag[sb];
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    y[b][0] = 0;
+                if (live) {
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        __builtin_memcpy(&y[b][0], in + off + (u32)b * 64u, 4);
+                }
+                ecgf::mul_xor_jt<1>(c, acc, y);
+            }
+            if (live) {
+                uint8_t *out = a.frag[brick] + off;
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    __builtin_memcpy(out + (u32)b * 64u, &acc[b][0], 4);
+            }
+        }
+    }
+}
+
 /* Zero-copy variant for the host-buffer path, where every input and output
  * lives in pinned host memory and the CUs read and write it over PCIe
  * (ec_device.hip run_pipeline).  There the link, not HBM or the VALU, is the

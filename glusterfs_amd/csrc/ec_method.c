@@ -3034,6 +3034,176 @@ ecm_locate_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_
     return ecd_locate(device, stream, &d, s.check, s.cb, s.bb, ratio, loc);
 }
 
+/* ------------------------------------------- repairing the named chunks */
+
+/* Weak like ecd_locate: without the symbol ec_method_repair_device is
+ * -ENODEV. */
+extern __typeof__(ecd_repair) ecd_repair __attribute__((weak));
+
+/* What both entry points derive from avail_mask: bset[] = its k + 1 lowest
+ * bricks (locate's basis B, then c0, the first brick after it), and for
+ * every brick i of avail the row coef[i * k ..] of k coefficients that
+ * predicts its chunk from B_i, the k lowest bricks of avail other than i:
+ * B when i is a check brick, else B without i and with c0, still ascending. */
+typedef struct {
+    uint8_t bset[ECM_MAX_K + 1];
+    uint8_t coef[ECM_MAX_N * ECM_MAX_K];
+} ecm_repair_sets_t;
+
+static int
+repair_args(ec_matrix_list_t *list, uintptr_t avail_mask, void *const *frags,
+            const uint32_t *loc, ecm_repair_sets_t *s)
+{
+    uint32_t i, nb = 0;
+
+    if (!list || !CTX(list) || !frags || !loc || ((uintptr_t)loc & 3u))
+        return -EINVAL;
+    if ((avail_mask >> list->rows) != 0 || popcount_mask(avail_mask) < list->columns + 1)
+        return -EINVAL;
+    for (i = 0; i < list->rows; i++) {
+        if (!((avail_mask >> i) & 1))
+            continue;
+        if (!frags[i])
+            return -EINVAL;
+        if (nb <= list->columns)
+            s->bset[nb++] = (uint8_t)i;
+    }
+    return 0;
+}
+
+/* One heal_pattern per brick of avail: the inputs of B_i are the first k
+ * entries of bset[] that are not brick i (all of B for a check brick). */
+static int
+repair_tables(ec_matrix_list_t *list, uintptr_t avail_mask, ecm_repair_sets_t *s)
+{
+    const uint32_t k = list->columns;
+    uint8_t pat[ECM_MAX_K + ECM_MAX_K];
+    uint32_t rows[ECM_MAX_K], i, p, nb, nt;
+    uintptr_t bmask;
+    int rc;
+
+    for (i = 0; i < list->rows; i++) {
+        if (!((avail_mask >> i) & 1))
+            continue;
+        bmask = 0;
+        for (p = 0, nb = 0; p <= k && nb < k; p++)
+            if (s->bset[p] != i) {
+                bmask |= (uintptr_t)1 << s->bset[p];
+                nb++;
+            }
+        rows_from_mask(bmask, rows);
+        if (!mask_rows_ok(list, bmask, rows))
+            return -EINVAL;
+        nt = 0;
+        rc = heal_pattern(list, bmask, rows, (uintptr_t)1 << i, pat, &nt);
+        if (rc)
+            return rc;
+        if (nt != 1)
+            return -EINVAL;
+        memcpy(s->coef + i * k, pat + k, k);
+    }
+    return 0;
+}
+
+static int32_t
+ecm_repair_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                void *const *frags, const uint32_t *loc, uint64_t *nrepaired,
+                uint64_t *nskipped)
+{
+    ecm_repair_sets_t s;
+    ecd_combine_desc_t d;
+    uint32_t i, p, q, k, w;
+    uint64_t t, e, done = 0, skipped = 0;
+    int rc;
+
+    rc = repair_args(list, avail_mask, frags, loc, &s);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    k = list->columns;
+    /* host entry point: device buffers go to _device */
+    for (i = 0; i < list->rows; i++)
+        if (((avail_mask >> i) & 1) && ecd_ptr_device(frags[i]) >= 0)
+            return -EINVAL;
+    if (ecd_ptr_device(loc) >= 0)
+        return -EINVAL;
+    rc = repair_tables(list, avail_mask, &s);
+    if (rc)
+        return rc;
+    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+    d.k = k;
+    d.rows = 1;
+    d.npatterns = 1;
+    d.pat_bytes = 2 * k;
+    d.in_stride = EC_METHOD_CHUNK_SIZE;
+    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    for (p = 0; p < k; p++)
+        d.pat[p] = (uint8_t)p;
+    /* clean stripes cost the scan; a run of stripes naming one brick is one
+     * 1 x k combination straight into that brick's fragment */
+    for (t = 0; t < nstripes; t = e) {
+        w = loc[t];
+        e = t + 1;
+        if (w == 0)
+            continue;
+        if ((w & (w - 1u)) != 0 || ((uintptr_t)w & avail_mask) == 0) {
+            skipped++;
+            continue;
+        }
+        while (e < nstripes && loc[e] == w)
+            e++;
+        i = (uint32_t)__builtin_ctz(w);
+        for (p = 0, q = 0; p < k; p++, q++) {
+            if (s.bset[q] == i)
+                q++;
+            d.in_base[p] = (const uint8_t *)frags[s.bset[q]] + t * EC_METHOD_CHUNK_SIZE;
+        }
+        d.out_base[0] = (uint8_t *)frags[i] + t * EC_METHOD_CHUNK_SIZE;
+        d.nstripes = e - t;
+        memcpy(d.pat + k, s.coef + i * k, k);
+        rc = ecc_combine(CTX(list)->isa, &d);
+        if (rc)
+            return rc;
+        done += e - t;
+    }
+    if (nrepaired)
+        *nrepaired = done;
+    if (nskipped)
+        *nskipped = skipped;
+    return 0;
+}
+
+static int32_t
+ecm_repair_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                       uintptr_t avail_mask, void *const *frags, const uint32_t *loc)
+{
+    ecm_repair_sets_t s;
+    uint32_t i;
+    int rc;
+
+    rc = repair_args(list, avail_mask, frags, loc, &s);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    /* device entry point: every buffer lives on `device` */
+    if (device < 0)
+        return -EINVAL;
+    for (i = 0; i < list->rows; i++)
+        if (((avail_mask >> i) & 1) && ecd_ptr_device(frags[i]) != device)
+            return -EINVAL;
+    if (ecd_ptr_device(loc) != device)
+        return -EINVAL;
+    if (!ecd_repair)
+        return -ENODEV;
+    rc = repair_tables(list, avail_mask, &s);
+    if (rc)
+        return rc;
+    return ecd_repair(device, stream, list->columns, nstripes, frags, (uint32_t)avail_mask,
+                      s.bset, s.coef, loc);
+}
+
 /* ------------------------------------------------- partial-stripe writes */
 
 static int32_t
@@ -3422,6 +3592,26 @@ ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream, uint64
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_locate_device", seq,
                    ecm_locate_device_impl(list, device, stream, nstripes, avail_mask, frags,
+                                          loc));
+}
+
+int32_t
+ec_method_repair(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                 void *const *frags, const uint32_t *loc, uint64_t *nrepaired,
+                 uint64_t *nskipped)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_repair", seq,
+                   ecm_repair_impl(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped));
+}
+
+int32_t
+ec_method_repair_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                        uintptr_t avail_mask, void *const *frags, const uint32_t *loc)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_repair_device", seq,
+                   ecm_repair_device_impl(list, device, stream, nstripes, avail_mask, frags,
                                           loc));
 }
 

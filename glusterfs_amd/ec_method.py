@@ -54,6 +54,7 @@ EXPORTS = (
     "ec_method_xover_observe", "ec_method_xover_reset", "ec_method_encode_rows",
     "ec_method_encode_rows_device", "ec_method_verify", "ec_method_verify_device",
     "ec_method_locate", "ec_method_locate_device",
+    "ec_method_repair", "ec_method_repair_device",
 )
 
 
@@ -161,6 +162,9 @@ def _load():
         "ec_method_verify_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
         "ec_method_locate": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64)]),
         "ec_method_locate_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
+        "ec_method_repair": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64),
+                                   ctypes.POINTER(u64)]),
+        "ec_method_repair_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_encode_device": (i32, [P, ctypes.c_int, vp, u64, vp, vp]),
         "ec_method_decode_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_decode_mixed_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, u32, vp,
@@ -549,6 +553,18 @@ class ECMatrixList:
                "ec_method_locate")
         return nbad.value
 
+    def repair(self, nstripes, avail_mask, frags, loc):
+        """ec_method_repair: where loc[t] is 1 << brick for a brick of
+        avail_mask (k + 1 bricks are enough), rewrite chunk t of that brick's
+        fragment from the k lowest other bricks; every other stripe is left
+        alone.  Returns (nrepaired, nskipped).  For what a scrub finds: a
+        wholly bad brick is heal's job."""
+        done, skipped = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib.ec_method_repair(ctypes.byref(self._list), nstripes, avail_mask,
+                                    _ptr_array(frags), addr(loc), ctypes.byref(done),
+                                    ctypes.byref(skipped)), "ec_method_repair")
+        return done.value, skipped.value
+
     # --- device-resident, asynchronous --------------------------------------
     def encode_rows_device(self, device, stream, nstripes, inp, row_mask, out):
         """ec_method_encode_rows_device: out[i] (None where the bit of
@@ -595,6 +611,13 @@ class ECMatrixList:
         return _check(lib.ec_method_locate_device(ctypes.byref(self._list), device, stream,
                                                   nstripes, avail_mask, _ptr_array(frags),
                                                   addr(loc)), "ec_method_locate_device")
+
+    def repair_device(self, device, stream, nstripes, avail_mask, frags, loc):
+        """ec_method_repair_device: the same on device buffers (`loc` too),
+        queued on `stream`; nothing is counted."""
+        return _check(lib.ec_method_repair_device(ctypes.byref(self._list), device, stream,
+                                                  nstripes, avail_mask, _ptr_array(frags),
+                                                  addr(loc)), "ec_method_repair_device")
 
 
 def sync_device(device, stream=None):

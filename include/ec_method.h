@@ -244,6 +244,53 @@ int32_t ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream
                                 uint64_t nstripes, uintptr_t avail_mask,
                                 const void *const *frags, uint32_t *loc);
 
+/* Repairing what locate named: one call that consumes loc[] where it lies and
+ * rewrites only the named chunks, closing verify -> locate -> repair.  frags
+ * and avail_mask as for ec_method_locate, except that a >= k + 1 bricks are
+ * enough (k others determine a chunk), so a caller that learned the bad brick
+ * another way, a checksum for example, can use it with k + 1 fragments.
+ * loc[t] is read and never written.
+ *
+ * Where loc[t] == 1u << i with brick i in avail_mask, chunk t of frags[i] is
+ * overwritten with E_i * inv(B_i) applied to the chunks of B_i, the k lowest
+ * bricks of avail_mask other than i (the encode of the decode of those k
+ * chunks, row i).  Every other value leaves stripe t byte for byte as it was:
+ * 0, EC_MI355X_LOCATE_MANY alone or ORed with anything, two or more bits, the
+ * bit of a brick outside avail_mask or at or above n.  None of these is an
+ * error: the device variant sees them only on the GPU, so neither engine
+ * reports them.  Only chunk t of the named brick is written: nothing past
+ * nstripes*512, no other brick.
+ *
+ * With loc[] from ec_method_locate on the same frags and avail_mask, every
+ * stripe that locate named with a single brick is mutually consistent again
+ * and a second locate gives 0 for it.  As said there, with a - k == 2 two
+ * damaged chunks can imitate one: repair then writes what the code implies,
+ * not what was originally stored.  A wholly bad brick is ec_method_heal's
+ * job (one pattern, dense streaming); this call is for what a scrub finds.
+ *
+ * *nrepaired (host variant, may be NULL) = stripes rewritten; *nskipped (may
+ * be NULL) = stripes with loc[t] != 0 that were left alone.  The device
+ * variant counts nothing: the caller already holds loc[].
+ *
+ * -EINVAL: a NULL list, frags or loc; loc not 4-byte aligned; a bit of
+ * avail_mask at or above n; fewer than k + 1 bits; a NULL frags[i] for a set
+ * bit; host and device buffers mixed, or given to the wrong entry point (the
+ * device variant wants every buffer, loc included, on `device`).
+ * nstripes == 0 returns 0 after these checks and touches nothing.
+ *
+ * Like ec_method_locate, the host variant runs on the calling thread's CPU
+ * engine whatever the volume's engine is and leaves ec_method_stats_t, the
+ * router and the run-time compiler alone; the device variant is asynchronous
+ * on `stream` (locate and repair can be queued back to back with no host
+ * synchronisation between them), pre-zeroes nothing and uses no global
+ * atomics (-ENODEV where the device layer lacks it). */
+int32_t ec_method_repair(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                         void *const *frags, const uint32_t *loc,
+                         uint64_t *nrepaired, uint64_t *nskipped);
+int32_t ec_method_repair_device(ec_matrix_list_t *list, int device, void *stream,
+                                uint64_t nstripes, uintptr_t avail_mask,
+                                void *const *frags, const uint32_t *loc);
+
 /* Partial-stripe write: the read-modify-write of
  * ec_writev_start (ec-inode-write.c:1987-2085) fused with ec_writev_encode.
  * The write's user data is the iovec list iov[0..count) (as the writev fop
