@@ -83,6 +83,16 @@ int ecd_verify(int device, void *stream, const ecd_combine_desc_t *d, const void
 int ecd_locate(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                uint32_t *loc);
+/* Locating up to two damaged bricks (ec_method_locate2_device): the
+ * arguments of ecd_locate with d->rows >= 4, then ratio1[(r - 2) * k + p] =
+ * G[r][p] / G[1][p] for the rows after the second, and for every pair of
+ * inputs p < q, in lexicographic order, the 4 bytes {a, b, c, d} of
+ * inv([[G[0][p], G[0][q]], [G[1][p], G[1][q]]]) in pair_inv.  loc[t] gets 0,
+ * the bits of the one or two bricks that explain stripe t's mismatch, or bit
+ * 31 for none. */
+int ecd_locate2(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
+                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+                const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc);
 /* Repairing what locate named (ec_method_repair_device): frags[] is indexed
  * by brick and read for the bits of avail (no bit at or above 31); bset is
  * the k + 1 lowest bricks of avail, ascending: the basis B of ecd_locate and

@@ -25,6 +25,10 @@ int ecdk_verify(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
 int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                 uint32_t *loc);
+/* the one or two damaged bricks per stripe of ecd_locate2 (ec_locate2_n) */
+int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc);
 /* rewriting the chunks loc[] names, of ecd_repair (ec_repair_n) */
 int ecdk_repair(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
                 const uint8_t *bset, const uint8_t *coef, const uint32_t *loc);

@@ -18,6 +18,8 @@
  *            check fragments staged beside the basis, 4 bytes out per stripe
  *   locate   the damaged brick per stripe: ec_locate_n, verify's tile with
  *            the syndromes kept in LDS and a second phase for dirty tiles
+ *   locate2  up to two damaged bricks per stripe: ec_locate2_n, locate's two
+ *            phases and a third over the candidate pairs for open tiles
  *   repair   the chunks locate named: ec_repair_n, a ballot scan of loc[]
  *            and up to four dirty stripes of one brick per wave, no LDS
  *   stores   non-temporal on every device-path kernel except the 2+1 / 4+2
@@ -984,14 +986,12 @@ int launch_locate_k(hipStream_t s, const LocateArgs &a)
 
 } // namespace
 
-/* d, check, check_brick: as ecdk_verify, with at least two rows;
- * basis_brick[p]: brick index of input p; ratio: (rows - 1) x k bytes,
- * coefficient of row r over that of row 0; loc: nstripes device dwords. */
-int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
-                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
-                uint32_t *loc)
+/* The arguments of ec_locate_n from what ecdk_locate is given; *align gets
+ * the OR of the input addresses (the staging policy wants it). */
+static int pack_locate(const ecd_combine_desc_t *d, const void *const *check,
+                       const uint8_t *check_brick, const uint8_t *basis_brick,
+                       const uint8_t *ratio, uint32_t *loc, LocateArgs &a, uintptr_t *align)
 {
-    LocateArgs a;
     if (d->k == 0 || d->k > ECD_MAX_K || d->rows < 2 || d->k + d->rows >= ECD_MAX_ROWS ||
         d->npatterns != 1 || d->pat_ext || d->group_pattern ||
         d->pat_bytes < d->k + d->rows * d->k || d->in_stride != ECD_CHUNK || !check ||
@@ -1027,9 +1027,90 @@ int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
                                                       << ((p & 3u) * 8u);
         }
     }
+    *align = o;
+    return 0;
+}
+
+/* d, check, check_brick: as ecdk_verify, with at least two rows;
+ * basis_brick[p]: brick index of input p; ratio: (rows - 1) x k bytes,
+ * coefficient of row r over that of row 0; loc: nstripes device dwords. */
+int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+                uint32_t *loc)
+{
+    LocateArgs a;
+    uintptr_t o = 0;
+    if (int rc = pack_locate(d, check, check_brick, basis_brick, ratio, loc, a, &o))
+        return rc;
     /* the staging policy of ecdk_verify, by the bytes the call reads */
     const bool nt = nt_staging(a.nstripes * (a.k + a.rows) * ECD_CHUNK) && (o & 15u) == 0;
     return nt ? launch_locate_k<kLdsDmaNT>(s, a) : launch_locate_k<kLdsDmaDefault>(s, a);
+}
+
+/* ------------------------------------------ locating up to two bricks */
+
+namespace {
+
+template <int K, int NW, int LA>
+int launch_locate2(hipStream_t s, const Locate2Args &a)
+{
+    const uint64_t g = (a.l.nstripes + 3) / 4;
+    if (g == 0)
+        return 0;
+    if (g > 0x7fffffffull)
+        return -EINVAL;
+    /* at most 31 inputs (ecdk_locate2): 62 KiB + 48, under the 64 KiB a launch
+     * takes without raising the kernel's dynamic LDS limit */
+    const size_t lds = locate2_n_lds(a.l.k + a.l.rows);
+    hipLaunchKernelGGL((ec_locate2_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
+    return launch_ok("launch_locate2");
+}
+
+/* the buckets and wave counts of launch_locate_k */
+template <int LA>
+int launch_locate2_k(hipStream_t s, const Locate2Args &a)
+{
+    if (a.l.k <= 4)
+        return launch_locate2<4, 4, LA>(s, a);
+    if (a.l.k <= 8)
+        return a.l.nstripes <= (1u << 17) ? launch_locate2<8, 8, LA>(s, a)
+                                          : launch_locate2<8, 4, LA>(s, a);
+    return launch_locate2<16, 8, LA>(s, a);
+}
+
+} // namespace
+
+/* As ecdk_locate, with at least four rows.  ratio1: (rows - 2) x k bytes,
+ * coefficient of row r over that of row 1, for r >= 2; pair_inv: 4 bytes
+ * {a, b, c, d} per basis pair p < q in lexicographic order, the inverse of
+ * rows 0 and 1 of columns p and q (ec_kernels_impl.h, Locate2Args).  Every
+ * table travels in the kernel arguments: nothing is uploaded. */
+int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc)
+{
+    static_assert(sizeof(Locate2Args) <= 2048, "the tables must fit the kernel arguments");
+    Locate2Args a;
+    uintptr_t o = 0;
+    if (!ratio1 || !pair_inv || d->rows < 4)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    if (int rc = pack_locate(d, check, check_brick, basis_brick, ratio, loc, a.l, &o))
+        return rc;
+    const u32 k = a.l.k, kw = a.l.kw;
+    for (u32 r = 2; r < a.l.rows; ++r)
+        for (u32 p = 0; p < k; ++p)
+            a.ratio1[(r - 2) * kw + (p >> 2)] |= (u32)ratio1[(r - 2) * k + p] << ((p & 3u) * 8u);
+    u32 i = 0;
+    for (u32 p = 0; p < k; ++p)
+        for (u32 q = p + 1; q < k; ++q, ++i) {
+            memcpy(&a.pinv[i], pair_inv + 4u * i, 4);
+            a.ppq[i >> 2] |= (p << 4 | q) << ((i & 3u) * 8u);
+        }
+    a.npairs = i;
+    /* the staging policy of ecdk_locate, by the bytes the call reads */
+    const bool nt = nt_staging(a.l.nstripes * (k + a.l.rows) * ECD_CHUNK) && (o & 15u) == 0;
+    return nt ? launch_locate2_k<kLdsDmaNT>(s, a) : launch_locate2_k<kLdsDmaDefault>(s, a);
 }
 
 /* ------------------------------------------- repairing the named chunks */

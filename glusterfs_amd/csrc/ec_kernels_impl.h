@@ -1717,6 +1717,262 @@ constexpr size_t locate_n_lds(u32 inputs)
     return (size_t)inputs * 4 * ECD_CHUNK + 8 * sizeof(u32);
 }
 
+/* ------------------------------------------ locating up to two bricks */
+
+constexpr u32 kLocate2Pairs = ECD_MAX_K * (ECD_MAX_K - 1) / 2;   /* C(16, 2) */
+
+/* Kernel arguments of ec_locate2_n: LocateArgs, then what the pairs need.
+ * ratio1 holds q1[r][p] = G[r][p] / G[1][p] of rows 2 .. rows-1, laid out
+ * like l.ratio (row r at word (r - 2) * kw): the ratios against row 1, for a
+ * pair whose check brick is row 0.  Basis pair i (p < q, in lexicographic
+ * order) has the byte p << 4 | q in ppq and, in pinv[i], the four bytes
+ * {a, b, c, d} of inv([[G[0][p], G[0][q]], [G[1][p], G[1][q]]]), so that
+ * e_p = a * s_0 ^ b * s_1 and e_q = c * s_0 ^ d * s_1.  1,712 bytes in all:
+ * every table travels in the kernel arguments, whatever the geometry. */
+struct Locate2Args {
+    LocateArgs l;
+    u32 ratio1[kLocateWords];
+    u32 pinv[kLocate2Pairs];
+    u32 ppq[kLocate2Pairs / 4];
+    u32 npairs, pad;
+};
+
+/* ec_method_locate2_device: which one or two bricks' chunks are wrong?
+ * Phases 1 and 2 are ec_locate_n's, statement for statement: the tile, the
+ * syndromes kept in the check chunks' LDS slots, the block-uniform early exit
+ * of a clean tile, the basis position that alone explains a stripe.  A third
+ * word per stripe, flags[2T + s], collects the brick bits of a pair.
+ *
+ * After phase 2 a stripe is still open when three or more syndromes are
+ * non-zero and no basis position passed (exactly two non-zero syndromes are
+ * those two check bricks: nothing to compute).  A tile without an open
+ * stripe stores its four words and is done; that too is read from LDS after
+ * a barrier.  Phase 3 spreads 2k + C(k, 2) candidates over the waves:
+ *
+ *   (p, ref 0)   s_r == q[r][p] * s_0 for the rows r >= 1.  Exactly one row
+ *                that fails is the pair (basis p, that check brick): removing
+ *                it leaves an error in p alone.
+ *   (p, ref 1)   s_r == q1[r][p] * s_1 for the rows r >= 2: none failing is
+ *                the pair (basis p, check row 0).
+ *   (p, q)       e_p and e_q solved from rows 0 and 1, then s_r == G[r][p] *
+ *                e_p ^ G[r][q] * e_q for the rows r >= 2: none failing is
+ *                the pair of basis positions.
+ *
+ * All three are one loop over rows around one multiply site (the jump-table
+ * multiply is ~50 KiB of code per site): a step XORs up to two products into
+ * acc, then either keeps acc as e_p / e_q or compares it with s_r, the 16
+ * lanes of a stripe voting by ballot.  Every choice in it is wave-uniform.
+ * With a - k >= 4 at most one pair passes when no single brick does (two
+ * would make two codewords that agree on k positions), so the bits are ORed
+ * in LDS without ordering; a result that is not exactly two bits is MANY.
+ * No barrier sits in a loop.  Each loc[t] leaves by one plain dword store. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_locate2_n(const Locate2Args a)
+{
+    constexpr u32 T = 4;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 tid = threadIdx.x;
+    const u32 k = a.l.k, kw = a.l.kw, rows = a.l.rows, ni = k + rows;
+    const uint64_t t0 = (uint64_t)blockIdx.x * T;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    /* flags[s]: brick bits of stripe s's non-zero rows; flags[T + s]: the
+     * brick bit of the basis position that explains them; flags[2T + s]:
+     * the brick bits of the pair that does */
+    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
+    if (tid < 3 * T)
+        flags[tid] = 0;
+    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        return a.l.in[p] + st * ECD_CHUNK;
+    }, ni, t0, a.l.nstripes, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    uint8_t *col = lds + cs * 64u + cc * 4u;
+    const bool live = t0 + cs < a.l.nstripes;
+    for (u32 r = wave; r < rows; r += NW) {
+        const u32 rw = kw * r;
+        const u32 w0 = a.l.coef[rw];
+        const u32 w1 = K > 4 ? a.l.coef[rw + 1] : 0u;
+        const u32 w2 = K > 8 ? a.l.coef[rw + 2] : 0u;
+        const u32 w3 = K > 12 ? a.l.coef[rw + 3] : 0u;
+        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
+        u32 acc[8][1], y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            acc[b][0] = 0;
+#pragma unroll 1
+        for (u32 p = 0; p < k; ++p) {
+            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+            cl = (cl >> 8) | (ch << 56);
+            ch >>= 8;
+            if (c == 0)
+                continue;
+            const uint8_t *src = col + p * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+            ecgf::mul_xor_jt<1>(c, acc, y);
+        }
+        /* the syndrome replaces the stored chunk in LDS */
+        uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
+        u32 d = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (T * 64u));
+            const u32 s = acc[b][0] ^ *w;
+            *w = s;
+            d |= s;
+        }
+        const uint64_t vote = __ballot(live && d != 0);
+        const u32 brick = __builtin_amdgcn_readfirstlane((a.l.cbrick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
+        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
+            atomicOr(&flags[cs], 1u << brick);
+    }
+    __syncthreads();
+    const u32 any = __builtin_amdgcn_readfirstlane(flags[0] | flags[1] | flags[2] | flags[3]);
+    if (any == 0) {
+        if (tid < T && t0 + tid < a.l.nstripes)
+            a.l.loc[t0 + tid] = 0;
+        return;
+    }
+    /* a stripe with two or more non-zero rows looks for its basis position
+     * (stripes past nstripes have no flag) */
+    const u32 mine = flags[cs];
+    const bool open = (mine & (mine - 1u)) != 0;
+    const uint8_t *syn = col + k * (T * ECD_CHUNK);
+    for (u32 p = wave; p < k; p += NW) {
+        u32 y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            y[b][0] = *reinterpret_cast<const u32 *>(syn + (u32)b * (T * 64u));
+        u32 d = 0;
+#pragma unroll 1
+        for (u32 r = 1; r < rows; ++r) {
+            const u32 q = __builtin_amdgcn_readfirstlane(
+                (a.l.ratio[(r - 1) * kw + (p >> 2)] >> ((p & 3u) * 8u)) & 0xFFu);
+            u32 acc[8][1];
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                acc[b][0] = 0;
+            if (q != 0)
+                ecgf::mul_xor_jt<1>(q, acc, y);
+            const uint8_t *sr = syn + r * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
+        }
+        const uint64_t vote = __ballot(d != 0);
+        const u32 brick = __builtin_amdgcn_readfirstlane((a.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
+        if (cc == 0 && open && ((vote >> (cs * 16u)) & 0xFFFFu) == 0)
+            atomicOr(&flags[T + cs], 1u << brick);
+    }
+    __syncthreads();
+    /* open for a pair: three or more non-zero rows, no single position */
+    u32 need = 0;
+#pragma unroll
+    for (u32 s = 0; s < T; ++s)
+        need |= (u32)(__builtin_popcount(flags[s]) >= 3 && flags[T + s] == 0);
+    if (__builtin_amdgcn_readfirstlane(need) == 0) {
+        if (tid < T && t0 + tid < a.l.nstripes) {
+            const u32 f = flags[tid], b = flags[T + tid];
+            a.l.loc[t0 + tid] = __builtin_popcount(f) <= 1 ? f : b ? b : f;
+        }
+        return;
+    }
+    const bool open2 = __builtin_popcount(mine) >= 3 && flags[T + cs] == 0;
+    const u32 nitems = 2u * k + a.npairs;
+    for (u32 it = wave; it < nitems; it += NW) {
+        /* wave-uniform: a basis pair (p, q), or position p against row ref */
+        const bool pair = it >= 2u * k;
+        const u32 pi = pair ? it - 2u * k : 0u;
+        const u32 pq = __builtin_amdgcn_readfirstlane((a.ppq[pi >> 2] >> ((pi & 3u) * 8u)) & 0xFFu);
+        const u32 inv = __builtin_amdgcn_readfirstlane(a.pinv[pi]);
+        const u32 ref = pair ? 0u : it >= k ? 1u : 0u;
+        const u32 p = pair ? pq >> 4 : it - ref * k;
+        const u32 q = pq & 15u;
+        u32 ep[8][1], eq[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            ep[b][0] = eq[b][0] = 0;
+        u32 failed = 0;             /* rows of this lane's stripe that do not fit */
+#pragma unroll 1
+        for (u32 st = pair ? 0u : ref + 1u; st < rows; ++st) {
+            const bool solve = pair && st < 2u;
+            u32 acc[8][1], y[8][1];
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                acc[b][0] = 0;
+#pragma unroll 1
+            for (u32 j = 0; j < (pair ? 2u : 1u); ++j) {
+                u32 c;
+                if (!pair || solve) {
+                    /* from LDS: s_ref, or s_0 and s_1 */
+                    const u32 *tab = ref ? a.ratio1 : a.l.ratio;
+                    const u32 ri = pair ? 0u : (st - 1u - ref) * kw + (p >> 2);
+                    c = pair ? (inv >> ((2u * st + j) * 8u)) & 0xFFu
+                             : (tab[ri] >> ((p & 3u) * 8u)) & 0xFFu;
+                    const uint8_t *src = syn + (pair ? j : ref) * (T * ECD_CHUNK);
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+                } else {
+                    const u32 x = j ? q : p;
+                    c = (a.l.coef[st * kw + (x >> 2)] >> ((x & 3u) * 8u)) & 0xFFu;
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        y[b][0] = j ? eq[b][0] : ep[b][0];
+                }
+                c = __builtin_amdgcn_readfirstlane(c);
+                if (c != 0)
+                    ecgf::mul_xor_jt<1>(c, acc, y);
+            }
+            if (solve) {
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    if (st == 0)
+                        ep[b][0] = acc[b][0];
+                    else
+                        eq[b][0] = acc[b][0];
+                }
+                continue;
+            }
+            const uint8_t *sr = syn + st * (T * ECD_CHUNK);
+            u32 d = 0;
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
+            const uint64_t vote = __ballot(d != 0);
+            if (((vote >> (cs * 16u)) & 0xFFFFu) != 0)
+                failed |= 1u << st;
+        }
+        /* (p, ref 0): the one failing row is the pair's check brick;
+         * otherwise nothing may fail, and the second brick is row 0's, or q's */
+        const bool one = !pair && ref == 0;
+        const bool pass = one ? __builtin_popcount(failed) == 1 : failed == 0;
+        if (cc == 0 && open2 && pass) {
+            const u32 cr = one ? (u32)__builtin_ctz(failed) : 0u;
+            const u32 b0 = (a.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu;
+            const u32 b1 = pair ? (a.l.bbrick[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu
+                                : (a.l.cbrick[cr >> 2] >> ((cr & 3u) * 8u)) & 0xFFu;
+            atomicOr(&flags[2 * T + cs], (1u << b0) | (1u << b1));
+        }
+    }
+    __syncthreads();
+    if (tid < T && t0 + tid < a.l.nstripes) {
+        const u32 f = flags[tid], b = flags[T + tid], w = flags[2 * T + tid];
+        const u32 nz = __builtin_popcount(f);
+        a.l.loc[t0 + tid] = nz <= 1 ? f : b ? b : nz == 2 ? f
+                            : __builtin_popcount(w) == 2 ? w : kLocateMany;
+    }
+}
+
+/* dynamic LDS of an ec_locate2_n launch: the tile and three words per stripe */
+constexpr size_t locate2_n_lds(u32 inputs)
+{
+    return (size_t)inputs * 4 * ECD_CHUNK + 12 * sizeof(u32);
+}
+
 /* ------------------------------------------- repairing the named chunks */
 
 /* Kernel arguments of ec_repair_n.  frag[] is indexed by brick (null outside

@@ -2931,9 +2931,172 @@ locate_classify(int isa, const ecm_locate_sets_t *s, uint32_t k, const uint8_t *
     return 0;
 }
 
+/* ---- up to two bricks (ec_method_locate2) ---- */
+
+/* Weak like ecd_locate: without the symbol ec_method_locate2_device is
+ * -ENODEV. */
+extern __typeof__(ecd_locate2) ecd_locate2 __attribute__((weak));
+
+/* det of rows 0 and 1, columns p and q, of G (nr x k): not zero, every 2 x 2
+ * minor of an MDS code's parity part is regular. */
+static uint32_t
+pair_det(const uint8_t *G, uint32_t k, uint32_t p, uint32_t q)
+{
+    return ec_method_gf_mul(G[p], G[k + q]) ^ ec_method_gf_mul(G[q], G[k + p]);
+}
+
+/* What the device kernel wants beside locate_tables': ratio1[(r - 2) * k +
+ * p] = G[r][p] / G[1][p] for r >= 2, and per pair p < q (lexicographic) the
+ * bytes {a, b, c, d} of inv([[G0p, G0q], [G1p, G1q]]) = [[G1q, G0q], [G1p,
+ * G0p]] / det. */
+static int
+locate2_tables(uint32_t k, uint32_t nr, const uint8_t *G, uint8_t *ratio1, uint8_t *pinv)
+{
+    uint32_t r, p, q, v, det, i = 0;
+
+    for (r = 2; r < nr; r++)
+        for (p = 0; p < k; p++) {
+            v = ec_method_gf_div(G[r * k + p], G[k + p]);
+            if (v == 0 || v >= EC_GF_SIZE)
+                return -EINVAL;
+            ratio1[(r - 2) * k + p] = (uint8_t)v;
+        }
+    for (p = 0; p < k; p++)
+        for (q = p + 1; q < k; q++, i++) {
+            det = pair_det(G, k, p, q);
+            if (det == 0 || det >= EC_GF_SIZE)
+                return -EINVAL;
+            pinv[4 * i + 0] = (uint8_t)ec_method_gf_div(G[k + q], det);
+            pinv[4 * i + 1] = (uint8_t)ec_method_gf_div(G[q], det);
+            pinv[4 * i + 2] = (uint8_t)ec_method_gf_div(G[k + p], det);
+            pinv[4 * i + 3] = (uint8_t)ec_method_gf_div(G[p], det);
+        }
+    return 0;
+}
+
+/* Is syn[row] == c0 * syn[i0] (^ c1 * syn[i1] with two terms)?  One 1 x 1
+ * or 1 x 2 combine of the CPU engine; *eq gets the answer. */
+static int
+syn_fits(int isa, const uint8_t *syn, uint32_t row, uint32_t terms, uint32_t i0, uint32_t c0,
+         uint32_t i1, uint32_t c1, int *eq)
+{
+    ecd_combine_desc_t m;
+    uint8_t prod[EC_METHOD_CHUNK_SIZE] __attribute__((aligned(64)));
+    int rc;
+
+    if (c0 >= EC_GF_SIZE || c1 >= EC_GF_SIZE)
+        return -EINVAL;
+    memset(&m, 0, offsetof(ecd_combine_desc_t, pat));
+    m.k = terms;
+    m.rows = 1;
+    m.nstripes = 1;
+    m.npatterns = 1;
+    m.pat_bytes = 2 * terms;
+    m.in_stride = EC_METHOD_CHUNK_SIZE;
+    m.out_stride = EC_METHOD_CHUNK_SIZE;
+    m.in_base[0] = syn + (size_t)i0 * EC_METHOD_CHUNK_SIZE;
+    m.in_base[1] = syn + (size_t)i1 * EC_METHOD_CHUNK_SIZE;
+    m.out_base[0] = prod;
+    m.pat[0] = 0;
+    if (terms == 1) {
+        m.pat[1] = (uint8_t)c0;
+    } else {
+        m.pat[1] = 1;
+        m.pat[2] = (uint8_t)c0;
+        m.pat[3] = (uint8_t)c1;
+    }
+    rc = ecc_combine(isa, &m);
+    if (rc)
+        return rc;
+    *eq = memcmp(prod, syn + (size_t)row * EC_METHOD_CHUNK_SIZE, EC_METHOD_CHUNK_SIZE) == 0;
+    return 0;
+}
+
+/* The rare path of ec_method_locate2: locate_classify's answer stands unless
+ * it is MANY.  Then, in the order of ec_method.h: exactly two non-zero
+ * syndromes are those two check bricks; a basis brick b and a check brick c
+ * when, without row c, the syndromes are those of an error in b alone; two
+ * basis bricks b < b2 when every syn[r], r >= 2, is the combination of syn[0]
+ * and syn[1] that errors in b and b2 imply.  G is the nr x k prediction
+ * matrix (nr >= 4).  At most one pair passes, so the first one is taken. */
+static int
+locate2_classify(int isa, const ecm_locate_sets_t *s, uint32_t k, const uint8_t *G,
+                 const uint8_t *ratio, const uint8_t *syn, uint32_t *out)
+{
+    uint32_t r, b, b2, nz = 0, nzmask = 0, nfail, last, det, al, be;
+    int rc, eq;
+
+    rc = locate_classify(isa, s, k, ratio, syn, out);
+    if (rc || *out != EC_MI355X_LOCATE_MANY)
+        return rc;
+    for (r = 0; r < s->nr; r++)
+        if (!chunk_is_zero(syn + (size_t)r * EC_METHOD_CHUNK_SIZE)) {
+            nz++;
+            nzmask |= 1u << s->cb[r];
+        }
+    if (nz == 2) {
+        *out = nzmask;
+        return 0;
+    }
+    for (b = 0; b < k; b++) {
+        /* against row 0: one row that does not fit is the check brick */
+        nfail = 0;
+        last = 0;
+        for (r = 1; r < s->nr && nfail < 2; r++) {
+            rc = syn_fits(isa, syn, r, 1, 0, ratio[(r - 1) * k + b], 0, 0, &eq);
+            if (rc)
+                return rc;
+            if (!eq) {
+                nfail++;
+                last = r;
+            }
+        }
+        if (nfail == 1) {
+            *out = (1u << s->bb[b]) | (1u << s->cb[last]);
+            return 0;
+        }
+        /* against row 1, for the check brick of row 0 */
+        for (r = 2; r < s->nr; r++) {
+            rc = syn_fits(isa, syn, r, 1, 1, ec_method_gf_div(G[r * k + b], G[k + b]), 0, 0, &eq);
+            if (rc)
+                return rc;
+            if (!eq)
+                break;
+        }
+        if (r == s->nr) {
+            *out = (1u << s->bb[b]) | (1u << s->cb[0]);
+            return 0;
+        }
+    }
+    for (b = 0; b < k; b++)
+        for (b2 = b + 1; b2 < k; b2++) {
+            det = pair_det(G, k, b, b2);
+            if (det == 0 || det >= EC_GF_SIZE)
+                return -EINVAL;
+            for (r = 2; r < s->nr; r++) {
+                al = ec_method_gf_mul(G[r * k + b], G[k + b2]) ^
+                     ec_method_gf_mul(G[r * k + b2], G[k + b]);
+                be = ec_method_gf_mul(G[r * k + b], G[b2]) ^
+                     ec_method_gf_mul(G[r * k + b2], G[b]);
+                rc = syn_fits(isa, syn, r, 2, 0, ec_method_gf_div(al, det), 1,
+                              ec_method_gf_div(be, det), &eq);
+                if (rc)
+                    return rc;
+                if (!eq)
+                    break;
+            }
+            if (r == s->nr) {
+                *out = (1u << s->bb[b]) | (1u << s->bb[b2]);
+                return 0;
+            }
+        }
+    return 0;
+}
+
+/* Both host calls: `two` = ec_method_locate2 (a >= k + 4, pairs named). */
 static int32_t
-ecm_locate_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                const void *const *frags, uint32_t *loc, uint64_t *nbad)
+locate_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+            const void *const *frags, uint32_t *loc, uint64_t *nbad, int two)
 {
     ecm_locate_sets_t s;
     ecd_combine_desc_t d;
@@ -2947,6 +3110,8 @@ ecm_locate_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
     rc = locate_args(list, avail_mask, frags, loc, &s);
     if (rc)
         return rc;
+    if (two && s.nr < 4)
+        return -EINVAL;
     if (nstripes == 0)
         return 0;
     k = list->columns;
@@ -2987,7 +3152,9 @@ ecm_locate_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
                 for (p = 0; p < EC_METHOD_CHUNK_SIZE; p++)
                     syn[r * EC_METHOD_CHUNK_SIZE + p] = pr[p] ^ st[p];
             }
-            rc = locate_classify(CTX(list)->isa, &s, k, ratio, syn, &loc[s0 + t]);
+            rc = two ? locate2_classify(CTX(list)->isa, &s, k, d.pat + k, ratio, syn,
+                                        &loc[s0 + t])
+                     : locate_classify(CTX(list)->isa, &s, k, ratio, syn, &loc[s0 + t]);
             count++;
         }
     }
@@ -2998,18 +3165,36 @@ ecm_locate_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
 }
 
 static int32_t
-ecm_locate_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
-                       uintptr_t avail_mask, const void *const *frags, uint32_t *loc)
+ecm_locate_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                const void *const *frags, uint32_t *loc, uint64_t *nbad)
+{
+    return locate_host(list, nstripes, avail_mask, frags, loc, nbad, 0);
+}
+
+static int32_t
+ecm_locate2_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                 const void *const *frags, uint32_t *loc, uint64_t *nbad)
+{
+    return locate_host(list, nstripes, avail_mask, frags, loc, nbad, 1);
+}
+
+/* Both device calls: `two` = ec_method_locate2_device. */
+static int32_t
+locate_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+              uintptr_t avail_mask, const void *const *frags, uint32_t *loc, int two)
 {
     ecm_locate_sets_t s;
     ecd_combine_desc_t d;
-    uint8_t ratio[ECM_MAX_N * ECM_MAX_K];
+    uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ratio1[ECM_MAX_N * ECM_MAX_K];
+    uint8_t pinv[ECM_MAX_K * (ECM_MAX_K - 1) / 2 * 4];
     uint32_t p;
     int rc;
 
     rc = locate_args(list, avail_mask, frags, loc, &s);
     if (rc)
         return rc;
+    if (two && s.nr < 4)
+        return -EINVAL;
     if (nstripes == 0)
         return 0;
     /* device entry point: every buffer lives on `device` */
@@ -3023,15 +3208,33 @@ ecm_locate_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_
             return -EINVAL;
     if (ecd_ptr_device(loc) != device)
         return -EINVAL;
-    if (!ecd_locate)
+    if (two ? !ecd_locate2 : !ecd_locate)
         return -ENODEV;
     rc = locate_tables(list, &s, &d, ratio);
+    if (rc == 0 && two)
+        rc = locate2_tables(d.k, s.nr, d.pat + d.k, ratio1, pinv);
     if (rc)
         return rc;
     d.nstripes = nstripes;
     for (p = 0; p < d.k; p++)
         d.in_base[p] = s.in[p];
+    if (two)
+        return ecd_locate2(device, stream, &d, s.check, s.cb, s.bb, ratio, ratio1, pinv, loc);
     return ecd_locate(device, stream, &d, s.check, s.cb, s.bb, ratio, loc);
+}
+
+static int32_t
+ecm_locate_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                       uintptr_t avail_mask, const void *const *frags, uint32_t *loc)
+{
+    return locate_device(list, device, stream, nstripes, avail_mask, frags, loc, 0);
+}
+
+static int32_t
+ecm_locate2_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                        uintptr_t avail_mask, const void *const *frags, uint32_t *loc)
+{
+    return locate_device(list, device, stream, nstripes, avail_mask, frags, loc, 1);
 }
 
 /* ------------------------------------------- repairing the named chunks */
@@ -3593,6 +3796,25 @@ ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream, uint64
     return ecm_ret("ec_method_locate_device", seq,
                    ecm_locate_device_impl(list, device, stream, nstripes, avail_mask, frags,
                                           loc));
+}
+
+int32_t
+ec_method_locate2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                  const void *const *frags, uint32_t *loc, uint64_t *nbad)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_locate2", seq,
+                   ecm_locate2_impl(list, nstripes, avail_mask, frags, loc, nbad));
+}
+
+int32_t
+ec_method_locate2_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                         uintptr_t avail_mask, const void *const *frags, uint32_t *loc)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_locate2_device", seq,
+                   ecm_locate2_device_impl(list, device, stream, nstripes, avail_mask, frags,
+                                           loc));
 }
 
 int32_t

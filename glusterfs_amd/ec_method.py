@@ -55,6 +55,7 @@ EXPORTS = (
     "ec_method_encode_rows_device", "ec_method_verify", "ec_method_verify_device",
     "ec_method_locate", "ec_method_locate_device",
     "ec_method_repair", "ec_method_repair_device",
+    "ec_method_locate2", "ec_method_locate2_device",
 )
 
 
@@ -162,6 +163,8 @@ def _load():
         "ec_method_verify_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
         "ec_method_locate": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64)]),
         "ec_method_locate_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
+        "ec_method_locate2": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64)]),
+        "ec_method_locate2_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_repair": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64),
                                    ctypes.POINTER(u64)]),
         "ec_method_repair_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
@@ -553,6 +556,17 @@ class ECMatrixList:
                "ec_method_locate")
         return nbad.value
 
+    def locate2(self, nstripes, avail_mask, frags, loc):
+        """ec_method_locate2: which one or two bricks' chunks are wrong?  As
+        locate, with k + 4 bricks in avail_mask; `loc` gets 0, the bits of the
+        one or two bricks, or EC_MI355X_LOCATE_MANY; returns the number of
+        stripes with a non-zero entry."""
+        nbad = ctypes.c_uint64(0)
+        _check(lib.ec_method_locate2(ctypes.byref(self._list), nstripes, avail_mask,
+                                     _ptr_array(frags), addr(loc), ctypes.byref(nbad)),
+               "ec_method_locate2")
+        return nbad.value
+
     def repair(self, nstripes, avail_mask, frags, loc):
         """ec_method_repair: where loc[t] is 1 << brick for a brick of
         avail_mask (k + 1 bricks are enough), rewrite chunk t of that brick's
@@ -611,6 +625,13 @@ class ECMatrixList:
         return _check(lib.ec_method_locate_device(ctypes.byref(self._list), device, stream,
                                                   nstripes, avail_mask, _ptr_array(frags),
                                                   addr(loc)), "ec_method_locate_device")
+
+    def locate2_device(self, device, stream, nstripes, avail_mask, frags, loc):
+        """ec_method_locate2_device: the same on device buffers (`loc` too),
+        queued on `stream`."""
+        return _check(lib.ec_method_locate2_device(ctypes.byref(self._list), device, stream,
+                                                   nstripes, avail_mask, _ptr_array(frags),
+                                                   addr(loc)), "ec_method_locate2_device")
 
     def repair_device(self, device, stream, nstripes, avail_mask, frags, loc):
         """ec_method_repair_device: the same on device buffers (`loc` too),

@@ -244,6 +244,50 @@ int32_t ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream
                                 uint64_t nstripes, uintptr_t avail_mask,
                                 const void *const *frags, uint32_t *loc);
 
+/* Locating up to two damaged bricks.  Arguments, buffer rules, asynchrony
+ * and error codes are ec_method_locate's, except that avail_mask must name
+ * a >= k + 4 bricks: fewer bits are -EINVAL (so every call on a 2+1 or 4+2
+ * volume).  Restricted to those a bricks the code has distance a - k + 1 >=
+ * 5, so at most one codeword lies within two chunk positions of the a stored
+ * chunks of stripe t.  loc[t] (every loc[0..nstripes) written) is
+ *   0                       the a chunks are mutually consistent;
+ *   the OR of 1u << i       over the one or two bricks where the stored
+ *                           chunks differ from that codeword, when it exists:
+ *                           the smallest set S, |S| <= 2, whose removal
+ *                           leaves the other a - |S| chunks consistent;
+ *   EC_MI355X_LOCATE_MANY   otherwise.
+ * S is unique: two such sets would give codewords that agree on >= a - 4 >= k
+ * positions, hence one codeword, and the stored chunks would differ from it
+ * only on the intersection, a smaller set.  *nbad (host variant, may be NULL)
+ * = stripes with loc[t] != 0.
+ *
+ * What follows:
+ *   - wherever ec_method_locate on the same arguments gives 0 or a single
+ *     bit, ec_method_locate2 gives the same value;
+ *   - wherever locate gives MANY, locate2 gives two bits or MANY;
+ *   - one or two damaged chunks per stripe are always named correctly;
+ *   - with a - k >= 5, three damaged chunks are always MANY;
+ *   - with a - k == 4 three damaged chunks can imitate a pair (distance 5):
+ *     a property of the code, as the a - k == 2 caveat is for locate.
+ *
+ * Acting on a pair today: ec_method_repair leaves a stripe with two bits
+ * alone.  Call ec_method_heal[_device] on that stripe -- every pointer offset
+ * by t * 512, nstripes = 1 -- with mask = the k lowest bricks of avail_mask
+ * other than the named ones and target_mask = the named ones, and write the
+ * result back over the two chunks.
+ *
+ * Like ec_method_locate, the host variant runs on the calling thread's CPU
+ * engine whatever the volume's engine is and leaves ec_method_stats_t, the
+ * router and the run-time compiler alone; the device variant is asynchronous
+ * on `stream` with no host synchronisation (every table travels in the
+ * kernel arguments), pre-zeroes nothing, uses no global atomics and writes
+ * each loc[t] by one plain store (-ENODEV where the device layer lacks it). */
+int32_t ec_method_locate2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                          const void *const *frags, uint32_t *loc, uint64_t *nbad);
+int32_t ec_method_locate2_device(ec_matrix_list_t *list, int device, void *stream,
+                                 uint64_t nstripes, uintptr_t avail_mask,
+                                 const void *const *frags, uint32_t *loc);
+
 /* Repairing what locate named: one call that consumes loc[] where it lies and
  * rewrites only the named chunks, closing verify -> locate -> repair.  frags
  * and avail_mask as for ec_method_locate, except that a >= k + 1 bricks are
