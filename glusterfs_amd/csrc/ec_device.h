@@ -103,6 +103,18 @@ int ecd_locate2(int device, void *stream, const ecd_combine_desc_t *d, const voi
  * leaves stripe t alone. */
 int ecd_repair(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
                uint32_t avail, const uint8_t *bset, const uint8_t *coef, const uint32_t *loc);
+/* Repairing what locate2 named (ec_method_repair2_device): frags, avail and
+ * loc as for ecd_repair, with at least k + 2 bits in avail.  B is its k lowest
+ * bricks and the `rows` others, ascending, are the check bricks; g[r * k + p]
+ * is the heal matrix of the check bricks from B (the G of ecd_locate),
+ * ginv[r * k + p] = 1 / g[r * k + p] for rows 0 and 1, and pair_inv is
+ * ecd_locate2's.  Where loc[t] has one or two bits, all of bricks of avail,
+ * the named chunks of stripe t are overwritten with the prediction from the k
+ * lowest bricks of avail outside the named ones; any other value leaves
+ * stripe t alone. */
+int ecd_repair2(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
+                uint32_t avail, uint32_t rows, const uint8_t *g, const uint8_t *ginv,
+                const uint8_t *pair_inv, const uint32_t *loc);
 int ecd_sync(int device, void *stream);
 
 /* ---- host-memory entry points: stripes are partitioned across `ndev`

@@ -1665,6 +1665,19 @@ int ecd_repair(int device, void *stream, uint32_t k, uint64_t nstripes, void *co
     return ecdk_repair(pick_stream(stream), k, nstripes, frags, avail, bset, coef, loc);
 }
 
+int ecd_repair2(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
+                uint32_t avail, uint32_t rows, const uint8_t *g, const uint8_t *ginv,
+                const uint8_t *pair_inv, const uint32_t *loc)
+{
+    if (ecd_device_count() <= device || device < 0)
+        return -ENODEV;
+    DeviceGuard dg;
+    clear_stale_error();
+    HIPCHK(hipSetDevice(g_dev_ids[device]));
+    return ecdk_repair2(pick_stream(stream), k, nstripes, frags, avail, rows, g, ginv, pair_inv,
+                        loc);
+}
+
 int ecd_sync(int device, void *stream)
 {
     if (ecd_device_count() <= device || device < 0)

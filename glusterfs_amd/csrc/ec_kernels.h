@@ -32,6 +32,10 @@ int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *
 /* rewriting the chunks loc[] names, of ecd_repair (ec_repair_n) */
 int ecdk_repair(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
                 const uint8_t *bset, const uint8_t *coef, const uint32_t *loc);
+/* rewriting the one or two chunks loc[] names, of ecd_repair2 (ec_repair2_n) */
+int ecdk_repair2(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
+                 uint32_t rows, const uint8_t *g, const uint8_t *ginv, const uint8_t *pair_inv,
+                 const uint32_t *loc);
 /* Partial-stripe writes: materialise bytes [o0, o0+n) (n % 16 == 0) of the
  * virtual input {head[0:b1) | user[0:b2-b1) | tail[...]} into dst, and the
  * fused Vandermonde encode that reads interior stripes from user directly. */

@@ -22,6 +22,8 @@
  *            phases and a third over the candidate pairs for open tiles
  *   repair   the chunks locate named: ec_repair_n, a ballot scan of loc[]
  *            and up to four dirty stripes of one brick per wave, no LDS
+ *   repair2  the one or two chunks locate2 named: ec_repair2_n, repair's
+ *            scan, a pair rebuilt from the syndromes and locate2's tables
  *   stores   non-temporal on every device-path kernel except the 2+1 / 4+2
  *            register encoders (profiles/kbench_r01_nts.log)
  *   staging  LDS-DMA loads non-temporal for calls whose input exceeds the
@@ -1161,6 +1163,67 @@ int ecdk_repair(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags
         g = cap;
     hipLaunchKernelGGL(ec_repair_n, dim3((u32)g), dim3(kRepairThreads), 0, s, a);
     return launch_ok("launch_repair");
+}
+
+/* k, nstripes, frags, avail, loc: as ecdk_repair, with at least k + 2 bits in
+ * avail; rows = those bits less k; g: rows x k bytes, the heal matrix of the
+ * check bricks (the bricks of avail after its k lowest, ascending) from the k
+ * lowest; ginv: 2 x k bytes, 1 / g of its rows 0 and 1; pair_inv: as
+ * ecdk_locate2.  Every table travels in the kernel arguments: nothing is
+ * uploaded. */
+int ecdk_repair2(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
+                 uint32_t rows, const uint8_t *g, const uint8_t *ginv, const uint8_t *pair_inv,
+                 const uint32_t *loc)
+{
+    static_assert(sizeof(Repair2Args) <= 2048, "the tables must fit the kernel arguments");
+    Repair2Args a;
+    if (k == 0 || k > ECD_MAX_K || !frags || !g || !ginv || !pair_inv || !loc ||
+        ((uintptr_t)loc & 3u) || (avail >> 31) != 0 || rows < 2 ||
+        (u32)__builtin_popcount(avail) != k + rows)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    a.k = k;
+    a.kw = (k + 3) / 4;
+    a.avail = avail;
+    a.nstripes = nstripes;
+    a.loc = loc;
+    if (a.kw * rows > kRepair2Words)
+        return -EINVAL;
+    u32 nb = 0, nr = 0;
+    for (u32 i = 0; i < 31; ++i) {
+        if (!((avail >> i) & 1u))
+            continue;
+        if (!frags[i])
+            return -EINVAL;
+        a.frag[i] = static_cast<uint8_t *>(frags[i]);
+        if (nb < k) {
+            a.bmask |= 1u << i;
+            a.bbrick[nb >> 2] |= i << ((nb & 3u) * 8u);
+            ++nb;
+        } else {
+            a.cbrick[nr >> 2] |= i << ((nr & 3u) * 8u);
+            ++nr;
+        }
+    }
+    for (u32 r = 0; r < rows; ++r)
+        for (u32 p = 0; p < k; ++p) {
+            const u32 c = g[r * k + p];
+            if (c == 0)                 /* the code is MDS */
+                return -EINVAL;
+            a.g[r * a.kw + (p >> 2)] |= c << ((p & 3u) * 8u);
+            if (r < 2)
+                a.ginv[r][p >> 2] |= (u32)ginv[r * k + p] << ((p & 3u) * 8u);
+        }
+    memcpy(a.pinv, pair_inv, 4u * (k * (k - 1u) / 2u));
+    if (nstripes == 0)
+        return 0;
+    /* one lane per loc word; a few blocks per CU stride over the rest */
+    uint64_t grid = (nstripes + kRepairThreads - 1) / kRepairThreads;
+    const uint64_t cap = (uint64_t)cu_count() * 8u;
+    if (grid > cap)
+        grid = cap;
+    hipLaunchKernelGGL(ec_repair2_n, dim3((u32)grid), dim3(kRepairThreads), 0, s, a);
+    return launch_ok("launch_repair2");
 }
 
 /* Host-buffer combines with k <= 8 run the persistent double-buffered

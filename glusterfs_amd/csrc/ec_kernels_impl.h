@@ -2073,6 +2073,204 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair_n(const RepairArgs a
     }
 }
 
+/* ----------------------------------------- repairing up to two chunks */
+
+/* rows of G, kw words each: the most is ceil(k / 4) * (31 - k) at k = 13 */
+constexpr u32 kRepair2Words = 72;
+
+/* Kernel arguments of ec_repair2_n.  frag[] is indexed by brick (null outside
+ * avail); bmask is locate's basis B (the k lowest bricks of avail), bbrick the
+ * brick byte of every basis position and cbrick that of every check row (the
+ * other bricks of avail, ascending; rows 0 and 1 are c0 and c1).  g is G, the
+ * heal matrix of the check bricks from B, laid out like LocateArgs::coef (row
+ * r at word r * kw); ginv[r] holds 1 / G[r][p] for rows 0 and 1, a byte per
+ * position; pinv is Locate2Args::pinv, the pair p < q at index p * (2k - p -
+ * 1) / 2 + q - p - 1.  1,136 bytes: nothing is uploaded, whatever the
+ * geometry. */
+struct Repair2Args {
+    uint8_t *frag[ECD_MAX_ROWS];
+    const u32 *loc;
+    uint64_t nstripes;
+    u32 k, kw, avail, bmask;
+    u32 bbrick[ECD_MAX_K / 4];
+    u32 cbrick[ECD_MAX_ROWS / 4];
+    u32 g[kRepair2Words];
+    u32 ginv[2][ECD_MAX_K / 4];
+    u32 pinv[kLocate2Pairs];
+};
+
+/* ec_method_repair2_device: rewrite the one or two chunks loc[] names.  The
+ * scan is ec_repair_n's: the grid strides over loc[], a lane per word, and the
+ * ballot of "one or two bits, all of bricks in avail" is the wave's dirty set,
+ * empty in the normal case.  The wave takes the word of its first dirty lane
+ * and up to four dirty stripes of its 64 that hold the same word (so that
+ * every coefficient is wave-uniform), 16 lanes per stripe, a dword column of
+ * the 8 planes per lane, at byte addresses; it clears those bits and loops.
+ *
+ * There is no row per pair (C(31, 2) pairs would not fit the arguments): the
+ * named set S is rebuilt through the syndromes of the check rows against B,
+ * as ec_locate2_n tests its candidates.  With nb bricks of S in B (positions
+ * p < q) and nc among the check rows, the work is 2 nb + nc passes:
+ *
+ *   syndrome  nb of them: s = G[row] * x_B ^ x_row, for rows 0 and 1 when
+ *             nb = 2, else for row `ref` = 0, or 1 when S names row 0 itself;
+ *   solve     nb of them: x_p ^ s / G[ref][p], or with two positions x_p ^ (a
+ *             s_0 ^ b s_1) and x_q ^ (c s_0 ^ d s_1) from pinv; the corrected
+ *             chunk is stored and kept in registers;
+ *   predict   nc of them: G[row] * x_B with the corrected chunks in the place
+ *             of positions p and q, stored over the named check chunk.
+ *
+ * The bricks read are B_S (the k lowest bricks of avail outside S: B without
+ * p and q, with c0 and c1 as far as S leaves them) and S itself, and what is
+ * written is the one codeword that agrees with the stored chunks of B_S: the
+ * bytes of E * inv(B_S), as GF(2^8) has no rounding.  One brick named alone
+ * goes the same way (one syndrome, or one prediction) and gets the bytes of
+ * ec_repair_n.  All passes are one loop around one multiply site (the
+ * jump-table multiply is ~50 KiB of code per site), every choice in it
+ * wave-uniform; only loads and stores are predicated by `live`.
+ *
+ * Unlike in ec_repair_n, a written chunk may have been read before (a basis
+ * chunk enters its own syndrome).  Each lane writes only addresses it read
+ * itself, later in program order, and a stripe belongs to one wave: still no
+ * LDS, no barrier, no atomics. */
+__global__ __launch_bounds__(kRepairThreads) void ec_repair2_n(const Repair2Args a)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const u32 grp = lane >> 4, cc = lane & 15u;
+    const u32 k = a.k, kw = a.kw;
+    const u32 cmask = a.avail & ~a.bmask;
+    const uint64_t step = (uint64_t)gridDim.x * kRepairThreads;
+    for (uint64_t base = ((uint64_t)blockIdx.x * (kRepairThreads / 64u) + wave) * 64u;
+         base < a.nstripes; base += step) {
+        const uint64_t t = base + lane;
+        const u32 w = t < a.nstripes ? a.loc[t] : 0u;
+        /* MANY is bit 31 and avail has no bit at or above n <= 31 */
+        uint64_t dirty = __ballot(w != 0 && __builtin_popcount(w) <= 2 && (w & ~a.avail) == 0);
+        while (dirty != 0) {
+            const u32 first = __builtin_amdgcn_readfirstlane((u32)__builtin_ctzll(dirty));
+            const u32 wf = __builtin_amdgcn_readlane(w, first);
+            /* up to four stripes of the set that hold this word */
+            const uint64_t same = __ballot(w == wf) & dirty;
+            uint64_t rest = same;
+            u32 sel[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                sel[g] = rest ? (u32)__builtin_ctzll(rest) : 64u;
+                rest &= rest - 1u;
+            }
+            dirty &= ~(same ^ rest);
+            const u32 src = grp == 0 ? sel[0] : grp == 1 ? sel[1] : grp == 2 ? sel[2] : sel[3];
+            const bool live = src < 64u;
+            const uint64_t off = (base + src) * ECD_CHUNK + cc * 4u;
+            /* S: nb basis positions p < q and nc check rows r0 < r1 (basis
+             * bricks are below check bricks, so the low bit is p's if any) */
+            const u32 sb = wf & a.bmask, sc = wf & cmask;
+            const u32 nb = (u32)__builtin_popcount(sb), nc = (u32)__builtin_popcount(sc);
+            const u32 hi = 31u - (u32)__builtin_clz(wf);
+            const u32 p = sb ? (u32)__builtin_popcount(a.bmask & ((1u << __builtin_ctz(sb)) - 1u)) : 0u;
+            const u32 q = nb == 2 ? (u32)__builtin_popcount(a.bmask & ((1u << hi) - 1u)) : p;
+            const u32 r0 = sc ? (u32)__builtin_popcount(cmask & ((1u << __builtin_ctz(sc)) - 1u)) : 0u;
+            const u32 r1 = nc == 2 ? (u32)__builtin_popcount(cmask & ((1u << hi) - 1u)) : r0;
+            const u32 ref = nb == 1 && nc == 1 && r0 == 0 ? 1u : 0u;
+            const u32 pi = nb == 2 ? p * (2u * k - p - 1u) / 2u + (q - p - 1u) : 0u;
+            /* the solve coefficients {a, b, c, d}; one position: {1 / G[ref][p]} */
+            const u32 inv = __builtin_amdgcn_readfirstlane(
+                nb == 2 ? a.pinv[pi] : (a.ginv[ref][p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
+            u32 s0[8][1], s1[8][1], f0[8][1], f1[8][1];
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                s0[b][0] = s1[b][0] = f0[b][0] = f1[b][0] = 0;
+            const u32 npass = 2u * nb + nc;
+#pragma unroll 1
+            for (u32 ps = 0; ps < npass; ++ps) {
+                const bool syn = ps < nb, solve = !syn && ps < 2u * nb;
+                const u32 d = syn ? ps : ps - nb;               /* which syndrome / position */
+                const u32 row = syn ? (nb == 2 ? ps : ref) : ps - 2u * nb ? r1 : r0;
+                const u32 nterms = solve ? 2u : k;
+                u32 acc[8][1], y[8][1];
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    acc[b][0] = 0;
+#pragma unroll 1
+                for (u32 tm = 0; tm < nterms; ++tm) {
+                    u32 c;
+                    if (solve) {
+                        c = (inv >> ((2u * d + tm) * 8u)) & 0xFFu;
+#pragma unroll
+                        for (int b = 0; b < 8; ++b)
+                            y[b][0] = tm ? s1[b][0] : s0[b][0];
+                    } else {
+                        c = (a.g[row * kw + (tm >> 2)] >> ((tm & 3u) * 8u)) & 0xFFu;
+                        const bool fix0 = !syn && nb >= 1 && tm == p;
+                        const bool fix1 = !syn && nb == 2 && tm == q;
+                        if (fix0 || fix1) {
+#pragma unroll
+                            for (int b = 0; b < 8; ++b)
+                                y[b][0] = fix1 ? f1[b][0] : f0[b][0];
+                        } else {
+                            const u32 ib = __builtin_amdgcn_readfirstlane(
+                                (a.bbrick[tm >> 2] >> ((tm & 3u) * 8u)) & 0xFFu);
+                            const uint8_t *in = a.frag[ib];
+#pragma unroll
+                            for (int b = 0; b < 8; ++b)
+                                y[b][0] = 0;
+                            if (live) {
+#pragma unroll
+                                for (int b = 0; b < 8; ++b)
+                                    __builtin_memcpy(&y[b][0], in + off + (u32)b * 64u, 4);
+                            }
+                        }
+                    }
+                    c = __builtin_amdgcn_readfirstlane(c);
+                    if (c != 0)
+                        ecgf::mul_xor_jt<1>(c, acc, y);
+                }
+                /* the chunk this pass ends on: a check row's, or position d's */
+                const u32 pos = d ? q : p;
+                const u32 ob = __builtin_amdgcn_readfirstlane(
+                    solve ? (a.bbrick[pos >> 2] >> ((pos & 3u) * 8u)) & 0xFFu
+                          : (a.cbrick[row >> 2] >> ((row & 3u) * 8u)) & 0xFFu);
+                uint8_t *chunk = a.frag[ob] + off;
+                if (syn || solve) {
+                    if (live) {
+#pragma unroll
+                        for (int b = 0; b < 8; ++b) {
+                            u32 x;
+                            __builtin_memcpy(&x, chunk + (u32)b * 64u, 4);
+                            acc[b][0] ^= x;
+                        }
+                    }
+                }
+                if (syn) {
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) {
+                        if (d == 0)
+                            s0[b][0] = acc[b][0];
+                        else
+                            s1[b][0] = acc[b][0];
+                    }
+                    continue;
+                }
+                if (solve) {
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) {
+                        if (d == 0)
+                            f0[b][0] = acc[b][0];
+                        else
+                            f1[b][0] = acc[b][0];
+                    }
+                }
+                if (live) {
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        __builtin_memcpy(chunk + (u32)b * 64u, &acc[b][0], 4);
+                }
+            }
+        }
+    }
+}
+
 /* Zero-copy variant for the host-buffer path, where every input and output
  * lives in pinned host memory and the CUs read and write it over PCIe
  * (ec_device.hip run_pipeline).  There the link, not HBM or the VALU, is the

@@ -3253,15 +3253,17 @@ typedef struct {
     uint8_t coef[ECM_MAX_N * ECM_MAX_K];
 } ecm_repair_sets_t;
 
+/* `extra`: the bricks wanted beside k, 1 for repair and 2 for repair2 (k
+ * others must remain once the named ones are removed). */
 static int
 repair_args(ec_matrix_list_t *list, uintptr_t avail_mask, void *const *frags,
-            const uint32_t *loc, ecm_repair_sets_t *s)
+            const uint32_t *loc, uint32_t extra, ecm_repair_sets_t *s)
 {
     uint32_t i, nb = 0;
 
     if (!list || !CTX(list) || !frags || !loc || ((uintptr_t)loc & 3u))
         return -EINVAL;
-    if ((avail_mask >> list->rows) != 0 || popcount_mask(avail_mask) < list->columns + 1)
+    if ((avail_mask >> list->rows) != 0 || popcount_mask(avail_mask) < list->columns + extra)
         return -EINVAL;
     for (i = 0; i < list->rows; i++) {
         if (!((avail_mask >> i) & 1))
@@ -3308,18 +3310,51 @@ repair_tables(ec_matrix_list_t *list, uintptr_t avail_mask, ecm_repair_sets_t *s
     return 0;
 }
 
+/* The rows of a pair (ec_method_repair2): B_ij, the k lowest bricks of avail
+ * other than the two of `w`, into bricks[], and the 2 x k heal matrix of the
+ * pair from B_ij (row of the lower brick first) into coef[].  The inverse
+ * comes from the list's matrix cache like every other. */
+static int
+repair2_pair(ec_matrix_list_t *list, uintptr_t avail_mask, uint32_t w, uint8_t *bricks,
+             uint8_t *coef)
+{
+    const uint32_t k = list->columns;
+    uint8_t pat[ECM_MAX_K + 2 * ECM_MAX_K];
+    uint32_t rows[ECM_MAX_K], b, nb = 0, nt = 0;
+    uintptr_t bmask = 0;
+    int rc;
+
+    for (b = 0; b < list->rows && nb < k; b++)
+        if (((avail_mask >> b) & 1) && !((w >> b) & 1)) {
+            bmask |= (uintptr_t)1 << b;
+            bricks[nb++] = (uint8_t)b;
+        }
+    rows_from_mask(bmask, rows);
+    if (!mask_rows_ok(list, bmask, rows))
+        return -EINVAL;
+    rc = heal_pattern(list, bmask, rows, (uintptr_t)w, pat, &nt);
+    if (rc)
+        return rc;
+    if (nt != 2)
+        return -EINVAL;
+    memcpy(coef, pat + k, 2 * k);
+    return 0;
+}
+
+/* Both host calls: `two` = ec_method_repair2 (a >= k + 2, pairs rewritten). */
 static int32_t
-ecm_repair_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                void *const *frags, const uint32_t *loc, uint64_t *nrepaired,
-                uint64_t *nskipped)
+repair_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+            void *const *frags, const uint32_t *loc, uint64_t *nrepaired, uint64_t *nskipped,
+            int two)
 {
     ecm_repair_sets_t s;
     ecd_combine_desc_t d;
-    uint32_t i, p, q, k, w;
+    uint8_t pbricks[ECM_MAX_K], pcoef[2 * ECM_MAX_K];
+    uint32_t i, j, p, q, k, w, pw = 0;
     uint64_t t, e, done = 0, skipped = 0;
     int rc;
 
-    rc = repair_args(list, avail_mask, frags, loc, &s);
+    rc = repair_args(list, avail_mask, frags, loc, two ? 2 : 1, &s);
     if (rc)
         return rc;
     if (nstripes == 0)
@@ -3336,35 +3371,54 @@ ecm_repair_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
         return rc;
     memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
     d.k = k;
-    d.rows = 1;
     d.npatterns = 1;
-    d.pat_bytes = 2 * k;
     d.in_stride = EC_METHOD_CHUNK_SIZE;
     d.out_stride = EC_METHOD_CHUNK_SIZE;
     for (p = 0; p < k; p++)
         d.pat[p] = (uint8_t)p;
     /* clean stripes cost the scan; a run of stripes naming one brick is one
-     * 1 x k combination straight into that brick's fragment */
+     * 1 x k combination straight into that brick's fragment, a run naming one
+     * pair one 2 x k combination into the two (neither is an input: in place
+     * is safe) */
     for (t = 0; t < nstripes; t = e) {
         w = loc[t];
         e = t + 1;
         if (w == 0)
             continue;
-        if ((w & (w - 1u)) != 0 || ((uintptr_t)w & avail_mask) == 0) {
+        i = (uint32_t)__builtin_popcount(w);
+        if (i > (two ? 2u : 1u) || ((uintptr_t)w & ~avail_mask) != 0) {
             skipped++;
             continue;
         }
         while (e < nstripes && loc[e] == w)
             e++;
+        d.nstripes = e - t;
         i = (uint32_t)__builtin_ctz(w);
-        for (p = 0, q = 0; p < k; p++, q++) {
-            if (s.bset[q] == i)
-                q++;
-            d.in_base[p] = (const uint8_t *)frags[s.bset[q]] + t * EC_METHOD_CHUNK_SIZE;
+        if ((w & (w - 1u)) == 0) {
+            for (p = 0, q = 0; p < k; p++, q++) {
+                if (s.bset[q] == i)
+                    q++;
+                d.in_base[p] = (const uint8_t *)frags[s.bset[q]] + t * EC_METHOD_CHUNK_SIZE;
+            }
+            d.rows = 1;
+            memcpy(d.pat + k, s.coef + i * k, k);
+        } else {
+            /* the last pair's rows serve a run of stripes and its repeats */
+            if (w != pw) {
+                rc = repair2_pair(list, avail_mask, w, pbricks, pcoef);
+                if (rc)
+                    return rc;
+                pw = w;
+            }
+            j = (uint32_t)__builtin_ctz(w & (w - 1u));
+            for (p = 0; p < k; p++)
+                d.in_base[p] = (const uint8_t *)frags[pbricks[p]] + t * EC_METHOD_CHUNK_SIZE;
+            d.rows = 2;
+            d.out_base[1] = (uint8_t *)frags[j] + t * EC_METHOD_CHUNK_SIZE;
+            memcpy(d.pat + k, pcoef, 2 * k);
         }
         d.out_base[0] = (uint8_t *)frags[i] + t * EC_METHOD_CHUNK_SIZE;
-        d.nstripes = e - t;
-        memcpy(d.pat + k, s.coef + i * k, k);
+        d.pat_bytes = k + d.rows * k;
         rc = ecc_combine(CTX(list)->isa, &d);
         if (rc)
             return rc;
@@ -3378,14 +3432,40 @@ ecm_repair_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
 }
 
 static int32_t
-ecm_repair_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
-                       uintptr_t avail_mask, void *const *frags, const uint32_t *loc)
+ecm_repair_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                void *const *frags, const uint32_t *loc, uint64_t *nrepaired,
+                uint64_t *nskipped)
+{
+    return repair_host(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped, 0);
+}
+
+static int32_t
+ecm_repair2_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                 void *const *frags, const uint32_t *loc, uint64_t *nrepaired,
+                 uint64_t *nskipped)
+{
+    return repair_host(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped, 1);
+}
+
+/* Weak like ecd_repair: without the symbol ec_method_repair2_device is
+ * -ENODEV. */
+extern __typeof__(ecd_repair2) ecd_repair2 __attribute__((weak));
+
+/* Both device calls: `two` = ec_method_repair2_device. */
+static int32_t
+repair_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+              uintptr_t avail_mask, void *const *frags, const uint32_t *loc, int two)
 {
     ecm_repair_sets_t s;
-    uint32_t i;
+    ecm_locate_sets_t ls;
+    ecd_combine_desc_t d;
+    uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ratio1[ECM_MAX_N * ECM_MAX_K];
+    uint8_t pinv[ECM_MAX_K * (ECM_MAX_K - 1) / 2 * 4], ginv[2 * ECM_MAX_K];
+    const uint8_t *G;
+    uint32_t i, v;
     int rc;
 
-    rc = repair_args(list, avail_mask, frags, loc, &s);
+    rc = repair_args(list, avail_mask, frags, loc, two ? 2 : 1, &s);
     if (rc)
         return rc;
     if (nstripes == 0)
@@ -3398,13 +3478,48 @@ ecm_repair_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_
             return -EINVAL;
     if (ecd_ptr_device(loc) != device)
         return -EINVAL;
-    if (!ecd_repair)
+    if (two ? !ecd_repair2 : !ecd_repair)
         return -ENODEV;
-    rc = repair_tables(list, avail_mask, &s);
+    if (!two) {
+        rc = repair_tables(list, avail_mask, &s);
+        if (rc)
+            return rc;
+        return ecd_repair(device, stream, list->columns, nstripes, frags,
+                          (uint32_t)avail_mask, s.bset, s.coef, loc);
+    }
+    /* the tables of locate2: G, the heal matrix of the check bricks from the
+     * k lowest bricks, and the pair inverses; the kernel rebuilds any named
+     * set from them, so there is no row per pair */
+    rc = locate_args(list, avail_mask, (const void *const *)frags, loc, &ls);
+    if (rc == 0)
+        rc = locate_tables(list, &ls, &d, ratio);
+    if (rc == 0)
+        rc = locate2_tables(d.k, ls.nr, d.pat + d.k, ratio1, pinv);
     if (rc)
         return rc;
-    return ecd_repair(device, stream, list->columns, nstripes, frags, (uint32_t)avail_mask,
-                      s.bset, s.coef, loc);
+    G = d.pat + d.k;
+    for (i = 0; i < 2 * d.k; i++) {
+        v = ec_method_gf_div(1, G[i]);
+        if (v == 0 || v >= EC_GF_SIZE)
+            return -EINVAL;
+        ginv[i] = (uint8_t)v;
+    }
+    return ecd_repair2(device, stream, d.k, nstripes, frags, (uint32_t)avail_mask, ls.nr, G, ginv,
+                       pinv, loc);
+}
+
+static int32_t
+ecm_repair_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                       uintptr_t avail_mask, void *const *frags, const uint32_t *loc)
+{
+    return repair_device(list, device, stream, nstripes, avail_mask, frags, loc, 0);
+}
+
+static int32_t
+ecm_repair2_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                        uintptr_t avail_mask, void *const *frags, const uint32_t *loc)
+{
+    return repair_device(list, device, stream, nstripes, avail_mask, frags, loc, 1);
 }
 
 /* ------------------------------------------------- partial-stripe writes */
@@ -3835,6 +3950,26 @@ ec_method_repair_device(ec_matrix_list_t *list, int device, void *stream, uint64
     return ecm_ret("ec_method_repair_device", seq,
                    ecm_repair_device_impl(list, device, stream, nstripes, avail_mask, frags,
                                           loc));
+}
+
+int32_t
+ec_method_repair2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                  void *const *frags, const uint32_t *loc, uint64_t *nrepaired,
+                  uint64_t *nskipped)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_repair2", seq,
+                   ecm_repair2_impl(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped));
+}
+
+int32_t
+ec_method_repair2_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                         uintptr_t avail_mask, void *const *frags, const uint32_t *loc)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_repair2_device", seq,
+                   ecm_repair2_device_impl(list, device, stream, nstripes, avail_mask, frags,
+                                           loc));
 }
 
 int32_t

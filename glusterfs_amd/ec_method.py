@@ -56,6 +56,7 @@ EXPORTS = (
     "ec_method_locate", "ec_method_locate_device",
     "ec_method_repair", "ec_method_repair_device",
     "ec_method_locate2", "ec_method_locate2_device",
+    "ec_method_repair2", "ec_method_repair2_device",
 )
 
 
@@ -168,6 +169,9 @@ def _load():
         "ec_method_repair": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64),
                                    ctypes.POINTER(u64)]),
         "ec_method_repair_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
+        "ec_method_repair2": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64),
+                                    ctypes.POINTER(u64)]),
+        "ec_method_repair2_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_encode_device": (i32, [P, ctypes.c_int, vp, u64, vp, vp]),
         "ec_method_decode_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_decode_mixed_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, u32, vp,
@@ -579,6 +583,18 @@ class ECMatrixList:
                                     ctypes.byref(skipped)), "ec_method_repair")
         return done.value, skipped.value
 
+    def repair2(self, nstripes, avail_mask, frags, loc):
+        """ec_method_repair2: repair for what locate2 names.  Where loc[t] has
+        one or two bits, all of bricks of avail_mask (k + 2 bricks are
+        enough), rewrite chunk t of those bricks' fragments from the k lowest
+        other bricks; every other stripe is left alone.  Returns (nrepaired,
+        nskipped)."""
+        done, skipped = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib.ec_method_repair2(ctypes.byref(self._list), nstripes, avail_mask,
+                                     _ptr_array(frags), addr(loc), ctypes.byref(done),
+                                     ctypes.byref(skipped)), "ec_method_repair2")
+        return done.value, skipped.value
+
     # --- device-resident, asynchronous --------------------------------------
     def encode_rows_device(self, device, stream, nstripes, inp, row_mask, out):
         """ec_method_encode_rows_device: out[i] (None where the bit of
@@ -639,6 +655,13 @@ class ECMatrixList:
         return _check(lib.ec_method_repair_device(ctypes.byref(self._list), device, stream,
                                                   nstripes, avail_mask, _ptr_array(frags),
                                                   addr(loc)), "ec_method_repair_device")
+
+    def repair2_device(self, device, stream, nstripes, avail_mask, frags, loc):
+        """ec_method_repair2_device: the same on device buffers (`loc` too),
+        queued on `stream`; nothing is counted."""
+        return _check(lib.ec_method_repair2_device(ctypes.byref(self._list), device, stream,
+                                                   nstripes, avail_mask, _ptr_array(frags),
+                                                   addr(loc)), "ec_method_repair2_device")
 
 
 def sync_device(device, stream=None):

@@ -270,11 +270,11 @@ int32_t ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream
  *   - with a - k == 4 three damaged chunks can imitate a pair (distance 5):
  *     a property of the code, as the a - k == 2 caveat is for locate.
  *
- * Acting on a pair today: ec_method_repair leaves a stripe with two bits
- * alone.  Call ec_method_heal[_device] on that stripe -- every pointer offset
- * by t * 512, nstripes = 1 -- with mask = the k lowest bricks of avail_mask
- * other than the named ones and target_mask = the named ones, and write the
- * result back over the two chunks.
+ * Acting on a pair: ec_method_repair leaves a stripe with two bits alone;
+ * ec_method_repair2[_device], below, consumes loc[] where it lies and rewrites
+ * both chunks.  Its result for one stripe is that of ec_method_heal[_device]
+ * on that stripe with mask = the k lowest bricks of avail_mask other than the
+ * named ones and target_mask = the named ones.
  *
  * Like ec_method_locate, the host variant runs on the calling thread's CPU
  * engine whatever the volume's engine is and leaves ec_method_stats_t, the
@@ -334,6 +334,60 @@ int32_t ec_method_repair(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t av
 int32_t ec_method_repair_device(ec_matrix_list_t *list, int device, void *stream,
                                 uint64_t nstripes, uintptr_t avail_mask,
                                 void *const *frags, const uint32_t *loc);
+
+/* Repairing what locate2 named: ec_method_repair for loc[] values of one or
+ * two bits, closing verify -> locate2 -> repair2 on one stream.  Arguments,
+ * buffer rules, asynchrony and error codes are ec_method_repair's, except that
+ * avail_mask must name a >= k + 2 bricks (k others must remain once a pair is
+ * removed): fewer bits are -EINVAL, so every call on a 2+1 volume.  a = k + 2
+ * is enough: a caller that learned the pair another way, from checksums for
+ * example, can use the call where ec_method_locate2 (a >= k + 4) cannot run,
+ * on a 4+2 volume with every brick for instance.  loc[t] is read and never
+ * written.
+ *
+ * Let S be the set of bricks whose bits are set in loc[t].
+ *   |S| = 1, the brick in avail_mask: exactly what ec_method_repair does,
+ *       byte for byte (B_i = the k lowest bricks of avail_mask other than i).
+ *   |S| = 2, both bricks i < j in avail_mask: chunk t of frags[i] and chunk t
+ *       of frags[j] are overwritten with rows i and j of E * inv(B_ij)
+ *       applied to the stored chunks of B_ij, the k lowest bricks of
+ *       avail_mask other than i and j (the encode of the decode of those k
+ *       chunks).  For one stripe that is ec_method_heal with mask = B_ij and
+ *       target_mask = S.
+ *   Every other value leaves stripe t byte for byte as it was: 0,
+ *       EC_MI355X_LOCATE_MANY alone or ORed with anything, three or more
+ *       bits, a pair with one brick outside avail_mask or at or above n.
+ *       None of these is an error.
+ * Only the named chunks are written: no other brick, nothing past
+ * nstripes*512.
+ *
+ * With loc[] from ec_method_locate2 on the same frags and avail_mask, every
+ * stripe that locate2 named with one or two bits is mutually consistent
+ * afterwards and a second locate2 gives 0 for it.  With loc[] from
+ * ec_method_locate, repair2 does what ec_method_repair does.  The a - k == 4
+ * caveat of ec_method_locate2 carries over: three damaged chunks can imitate
+ * a pair, and repair2 then writes what the code implies, not what was
+ * originally stored.
+ *
+ * *nrepaired (host variant, may be NULL) = stripes rewritten, with one or two
+ * chunks; *nskipped (may be NULL) = stripes with loc[t] != 0 that were left
+ * alone.  The device variant counts nothing.
+ *
+ * -EINVAL: as ec_method_repair, with fewer than k + 2 bits in avail_mask.
+ * nstripes == 0 returns 0 after these checks and touches nothing.
+ *
+ * The host variant runs on the calling thread's CPU engine whatever the
+ * volume's engine is and leaves ec_method_stats_t, the router and the
+ * run-time compiler alone; the device variant is asynchronous on `stream`
+ * with no host synchronisation (every table travels in the kernel arguments,
+ * so locate2 and repair2 can be queued back to back), pre-zeroes nothing and
+ * uses no global atomics (-ENODEV where the device layer lacks it). */
+int32_t ec_method_repair2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                          void *const *frags, const uint32_t *loc,
+                          uint64_t *nrepaired, uint64_t *nskipped);
+int32_t ec_method_repair2_device(ec_matrix_list_t *list, int device, void *stream,
+                                 uint64_t nstripes, uintptr_t avail_mask,
+                                 void *const *frags, const uint32_t *loc);
 
 /* Partial-stripe write: the read-modify-write of
  * ec_writev_start (ec-inode-write.c:1987-2085) fused with ec_writev_encode.
