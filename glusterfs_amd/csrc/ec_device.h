@@ -83,6 +83,17 @@ int ecd_verify(int device, void *stream, const ecd_combine_desc_t *d, const void
 int ecd_locate(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                uint32_t *loc);
+/* A read that checks and corrects (ec_method_decode_checked_device): the
+ * arguments of ecd_locate with basis_brick ascending, then inv[j * k + p],
+ * the decode matrix of the k inputs (row j gives chunk j of a stripe's data),
+ * and ginv[p] = 1 / G[0][p].  loc[t] is ecd_locate's.  out (device memory,
+ * nstripes * k * 512 bytes, stripe-major like ecd_combine's decode output,
+ * any byte alignment) gets the decode of stripe t's k inputs, after the one
+ * input loc[t] names, if any, has been corrected to agree with the others. */
+int ecd_decode_checked(int device, void *stream, const ecd_combine_desc_t *d,
+                       const void *const *check, const uint8_t *check_brick,
+                       const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *inv,
+                       const uint8_t *ginv, void *out, uint32_t *loc);
 /* Locating up to two damaged bricks (ec_method_locate2_device): the
  * arguments of ecd_locate with d->rows >= 4, then ratio1[(r - 2) * k + p] =
  * G[r][p] / G[1][p] for the rows after the second, and for every pair of

@@ -1641,6 +1641,20 @@ int ecd_locate(int device, void *stream, const ecd_combine_desc_t *d, const void
     return ecdk_locate(pick_stream(stream), d, check, check_brick, basis_brick, ratio, loc);
 }
 
+int ecd_decode_checked(int device, void *stream, const ecd_combine_desc_t *d,
+                       const void *const *check, const uint8_t *check_brick,
+                       const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *inv,
+                       const uint8_t *ginv, void *out, uint32_t *loc)
+{
+    if (ecd_device_count() <= device || device < 0)
+        return -ENODEV;
+    DeviceGuard dg;
+    clear_stale_error();
+    HIPCHK(hipSetDevice(g_dev_ids[device]));
+    return ecdk_decode_checked(pick_stream(stream), d, check, check_brick, basis_brick, ratio, inv,
+                               ginv, out, loc);
+}
+
 int ecd_locate2(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc)

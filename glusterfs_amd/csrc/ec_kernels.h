@@ -25,6 +25,11 @@ int ecdk_verify(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
 int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                 uint32_t *loc);
+/* the checked and corrected decode of ecd_decode_checked (ec_decode_checked_n) */
+int ecdk_decode_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                        const uint8_t *check_brick, const uint8_t *basis_brick,
+                        const uint8_t *ratio, const uint8_t *inv, const uint8_t *ginv, void *out,
+                        uint32_t *loc);
 /* the one or two damaged bricks per stripe of ecd_locate2 (ec_locate2_n) */
 int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                  const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,

@@ -24,6 +24,8 @@
  *            and up to four dirty stripes of one brick per wave, no LDS
  *   repair2  the one or two chunks locate2 named: ec_repair2_n, repair's
  *            scan, a pair rebuilt from the syndromes and locate2's tables
+ *   checked  a read that checks and corrects: ec_decode_checked_n, locate's
+ *   decode   tile, the named basis chunk corrected in LDS, one dense decode
  *   stores   non-temporal on every device-path kernel except the 2+1 / 4+2
  *            register encoders (profiles/kbench_r01_nts.log)
  *   staging  LDS-DMA loads non-temporal for calls whose input exceeds the
@@ -1047,6 +1049,71 @@ int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
     /* the staging policy of ecdk_verify, by the bytes the call reads */
     const bool nt = nt_staging(a.nstripes * (a.k + a.rows) * ECD_CHUNK) && (o & 15u) == 0;
     return nt ? launch_locate_k<kLdsDmaNT>(s, a) : launch_locate_k<kLdsDmaDefault>(s, a);
+}
+
+/* ------------------------------------------- a read that checks and corrects */
+
+namespace {
+
+template <int K, int NW, int LA>
+int launch_decode_checked(hipStream_t s, const DecodeCheckedArgs &a)
+{
+    const uint64_t g = (a.l.nstripes + 3) / 4;
+    if (g == 0)
+        return 0;
+    if (g > 0x7fffffffull)
+        return -EINVAL;
+    /* the tile and the words of ec_locate_n: at most 62 KiB + 32 */
+    const size_t lds = locate_n_lds(a.l.k + a.l.rows);
+    hipLaunchKernelGGL((ec_decode_checked_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
+    return launch_ok("launch_decode_checked");
+}
+
+/* the buckets and wave counts of launch_locate_k */
+template <int LA>
+int launch_decode_checked_k(hipStream_t s, const DecodeCheckedArgs &a)
+{
+    if (a.l.k <= 4)
+        return launch_decode_checked<4, 4, LA>(s, a);
+    if (a.l.k <= 8)
+        return a.l.nstripes <= (1u << 17) ? launch_decode_checked<8, 8, LA>(s, a)
+                                          : launch_decode_checked<8, 4, LA>(s, a);
+    return launch_decode_checked<16, 8, LA>(s, a);
+}
+
+} // namespace
+
+/* As ecdk_locate, then inv: k x k bytes, the decode matrix of the basis (row
+ * j gives output chunk j); ginv: k bytes, 1 / coefficient of row 0; out:
+ * nstripes * k * 512 device bytes at any alignment.  Every table travels in
+ * the kernel arguments: nothing is uploaded. */
+int ecdk_decode_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                        const uint8_t *check_brick, const uint8_t *basis_brick,
+                        const uint8_t *ratio, const uint8_t *inv, const uint8_t *ginv, void *out,
+                        uint32_t *loc)
+{
+    static_assert(sizeof(DecodeCheckedArgs) <= 2048, "the tables must fit the kernel arguments");
+    DecodeCheckedArgs a;
+    uintptr_t o = 0;
+    if (!inv || !ginv || !out)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    if (int rc = pack_locate(d, check, check_brick, basis_brick, ratio, loc, a.l, &o))
+        return rc;
+    const u32 k = a.l.k, kw = a.l.kw;
+    a.out = static_cast<uint8_t *>(out);
+    for (u32 p = 0; p < k; ++p) {
+        if (ginv[p] == 0)
+            return -EINVAL;
+        a.bmask |= 1u << basis_brick[p];
+        a.ginv[p >> 2] |= (u32)ginv[p] << ((p & 3u) * 8u);
+        for (u32 j = 0; j < k; ++j)
+            a.inv[j * kw + (p >> 2)] |= (u32)inv[j * k + p] << ((p & 3u) * 8u);
+    }
+    /* the staging policy of ecdk_locate, by the bytes the call reads */
+    const bool nt = nt_staging(a.l.nstripes * (k + a.l.rows) * ECD_CHUNK) && (o & 15u) == 0;
+    return nt ? launch_decode_checked_k<kLdsDmaNT>(s, a)
+              : launch_decode_checked_k<kLdsDmaDefault>(s, a);
 }
 
 /* ------------------------------------------ locating up to two bricks */

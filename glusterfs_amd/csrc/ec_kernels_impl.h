@@ -1717,6 +1717,202 @@ constexpr size_t locate_n_lds(u32 inputs)
     return (size_t)inputs * 4 * ECD_CHUNK + 8 * sizeof(u32);
 }
 
+/* ------------------------------------------- a read that checks and corrects */
+
+/* Kernel arguments of ec_decode_checked_n: LocateArgs, then the decoded
+ * output (stripe t at out + t * k * 512, any byte alignment), B as a brick
+ * mask, inv(B) laid out like the coefficients (row j at word j * kw) and the
+ * k bytes 1 / G[0][p]. */
+struct DecodeCheckedArgs {
+    LocateArgs l;
+    uint8_t *out;
+    u32 bmask, pad;
+    u32 inv[ECD_MAX_K * (ECD_MAX_K / 4)];
+    u32 ginv[ECD_MAX_K / 4];
+};
+
+/* ec_method_decode_checked_device: decode the k lowest bricks and, in the
+ * same pass, check them against the others and correct a single bad chunk.
+ * Phases 1 and 2 are ec_locate_n's, statement for statement: the tile, the
+ * syndromes left in the check chunks' LDS slots, the flags and the result
+ * words.  A clean tile skips phase 2 and the correction.
+ *
+ * The correction, for a stripe whose result word names basis position p: the
+ * error in p is e = s_0 / G[0][p] (s_0 = G[0][p] * e when p alone is wrong),
+ * and XORing e into p's LDS slot puts the basis chunks on the one codeword
+ * the other a - 1 chunks lie on, so that one dense decode with inv(B) gives
+ * what inv(B_i) would give from the undamaged chunks.  The jump-table
+ * multiply wants a wave-uniform coefficient and p differs per stripe: the
+ * tile's four stripes go one per wave item, each on its own 16 lanes, around
+ * one multiply site.  MANY stripes, check-brick stripes and stripes past
+ * nstripes are left alone.
+ *
+ * The decode: the k output rows are spread over the waves like the check rows
+ * of phase 1; row j is the sum of inv(B)[j][p] * x_p over the basis slots and
+ * leaves by dword stores, 64 contiguous bytes per plane and stripe.  No
+ * barrier sits in a loop, and every decision around one is read from LDS
+ * after a barrier, so the whole block takes it together. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_decode_checked_n(const DecodeCheckedArgs a)
+{
+    constexpr u32 T = 4;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 tid = threadIdx.x;
+    const u32 k = a.l.k, ni = a.l.k + a.l.rows;
+    const uint64_t t0 = (uint64_t)blockIdx.x * T;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    /* flags[s], flags[T + s]: as in ec_locate_n */
+    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
+    if (tid < 2 * T)
+        flags[tid] = 0;
+    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        return a.l.in[p] + st * ECD_CHUNK;
+    }, ni, t0, a.l.nstripes, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    uint8_t *col = lds + cs * 64u + cc * 4u;
+    const bool live = t0 + cs < a.l.nstripes;
+    for (u32 r = wave; r < a.l.rows; r += NW) {
+        const u32 rw = a.l.kw * r;
+        const u32 w0 = a.l.coef[rw];
+        const u32 w1 = K > 4 ? a.l.coef[rw + 1] : 0u;
+        const u32 w2 = K > 8 ? a.l.coef[rw + 2] : 0u;
+        const u32 w3 = K > 12 ? a.l.coef[rw + 3] : 0u;
+        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
+        u32 acc[8][1], y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            acc[b][0] = 0;
+#pragma unroll 1
+        for (u32 p = 0; p < k; ++p) {
+            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+            cl = (cl >> 8) | (ch << 56);
+            ch >>= 8;
+            if (c == 0)
+                continue;
+            const uint8_t *src = col + p * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+            ecgf::mul_xor_jt<1>(c, acc, y);
+        }
+        /* the syndrome replaces the stored chunk in LDS */
+        uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
+        u32 d = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (T * 64u));
+            const u32 s = acc[b][0] ^ *w;
+            *w = s;
+            d |= s;
+        }
+        const uint64_t vote = __ballot(live && d != 0);
+        const u32 brick = __builtin_amdgcn_readfirstlane((a.l.cbrick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
+        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
+            atomicOr(&flags[cs], 1u << brick);
+    }
+    __syncthreads();
+    const u32 any = __builtin_amdgcn_readfirstlane(flags[0] | flags[1] | flags[2] | flags[3]);
+    if (any != 0) {
+        /* a stripe with two or more non-zero rows looks for its basis position
+         * (stripes past nstripes have no flag) */
+        const u32 mine = flags[cs];
+        const bool open = (mine & (mine - 1u)) != 0;
+        const uint8_t *s0 = col + k * (T * ECD_CHUNK);
+        for (u32 p = wave; p < k; p += NW) {
+            u32 y[8][1];
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(s0 + (u32)b * (T * 64u));
+            u32 d = 0;
+#pragma unroll 1
+            for (u32 r = 1; r < a.l.rows; ++r) {
+                const u32 q = __builtin_amdgcn_readfirstlane(
+                    (a.l.ratio[(r - 1) * a.l.kw + (p >> 2)] >> ((p & 3u) * 8u)) & 0xFFu);
+                u32 acc[8][1];
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    acc[b][0] = 0;
+                if (q != 0)
+                    ecgf::mul_xor_jt<1>(q, acc, y);
+                const uint8_t *sr = col + (k + r) * (T * ECD_CHUNK);
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
+            }
+            const uint64_t vote = __ballot(d != 0);
+            const u32 brick = __builtin_amdgcn_readfirstlane((a.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
+            if (cc == 0 && open && ((vote >> (cs * 16u)) & 0xFFFFu) == 0)
+                atomicOr(&flags[T + cs], 1u << brick);
+        }
+        __syncthreads();
+        /* stripe s of the tile, on lanes 16 s .. 16 s + 15 of one wave: its
+         * words are final, and a named basis brick is the one bit of the
+         * second while the first has two or more (0 for stripes past
+         * nstripes).  c = 0 (nothing to correct) multiplies to zero. */
+        for (u32 s = wave; s < T; s += NW) {
+            const u32 f = __builtin_amdgcn_readfirstlane(flags[s]);
+            const u32 bb = __builtin_amdgcn_readfirstlane(flags[T + s]);
+            const bool fix = (f & (f - 1u)) != 0 && bb != 0;
+            const u32 p = fix ? (u32)__builtin_popcount(a.bmask & (bb - 1u)) : 0u;
+            const u32 c = __builtin_amdgcn_readfirstlane(
+                fix ? (a.ginv[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu : 0u);
+            if (c == 0)
+                continue;
+            u32 acc[8][1], y[8][1];
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                acc[b][0] = 0;
+                y[b][0] = *reinterpret_cast<const u32 *>(s0 + (u32)b * (T * 64u));
+            }
+            ecgf::mul_xor_jt<1>(c, acc, y);
+            if (cs == s) {
+                uint8_t *x = col + p * (T * ECD_CHUNK);
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    *reinterpret_cast<u32 *>(x + (u32)b * (T * 64u)) ^= acc[b][0];
+            }
+        }
+        __syncthreads();
+    }
+    /* the decode of the (corrected) basis chunks */
+    uint8_t *o = a.out + (t0 + cs) * ((uint64_t)k * ECD_CHUNK) + cc * 4u;
+    for (u32 j = wave; j < k; j += NW) {
+        const u32 rw = a.l.kw * j;
+        const u32 w0 = a.inv[rw];
+        const u32 w1 = K > 4 ? a.inv[rw + 1] : 0u;
+        const u32 w2 = K > 8 ? a.inv[rw + 2] : 0u;
+        const u32 w3 = K > 12 ? a.inv[rw + 3] : 0u;
+        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
+        u32 acc[8][1], y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            acc[b][0] = 0;
+#pragma unroll 1
+        for (u32 p = 0; p < k; ++p) {
+            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+            cl = (cl >> 8) | (ch << 56);
+            ch >>= 8;
+            if (c == 0)
+                continue;
+            const uint8_t *src = col + p * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+            ecgf::mul_xor_jt<1>(c, acc, y);
+        }
+        if (live)
+            store_chunk<1, true>(o + j * ECD_CHUNK, acc);
+    }
+    if (tid < T && t0 + tid < a.l.nstripes) {
+        const u32 f = flags[tid], b = flags[T + tid];
+        a.l.loc[t0 + tid] = (f & (f - 1u)) == 0 ? f : b ? b : kLocateMany;
+    }
+}
+
 /* ------------------------------------------ locating up to two bricks */
 
 constexpr u32 kLocate2Pairs = ECD_MAX_K * (ECD_MAX_K - 1) / 2;   /* C(16, 2) */

@@ -3237,6 +3237,137 @@ ecm_locate2_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64
     return locate_device(list, device, stream, nstripes, avail_mask, frags, loc, 1);
 }
 
+/* ------------------------------------------- a read that checks and corrects */
+
+/* Weak like ecd_locate: without the symbol ec_method_decode_checked_device is
+ * -ENODEV. */
+extern __typeof__(ecd_decode_checked) ecd_decode_checked __attribute__((weak));
+
+/* The mask stripe t is decoded with: B, or B_i = B without i and with c0 (the
+ * lowest check brick) when loc[t] names basis brick i.  MANY is bit 31 and no
+ * mask has a bit there. */
+static uintptr_t
+checked_mask(const ecm_locate_sets_t *s, uint32_t w)
+{
+    if (((uintptr_t)w & s->bmask) == 0)
+        return s->bmask;
+    return (s->bmask & ~(uintptr_t)w) | (s->rmask & (~s->rmask + 1));
+}
+
+static int32_t
+ecm_decode_checked_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                        const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
+                        uint64_t *nmany)
+{
+    ecm_locate_sets_t s;
+    ecd_combine_desc_t d;
+    uint64_t t, t1, bad = 0, many = 0;
+    uintptr_t mask, cur = 0;
+    uint32_t k, r, b;
+    int rc;
+
+    rc = locate_args(list, avail_mask, frags, loc, &s);
+    if (rc)
+        return rc;
+    if (!out)
+        return -EINVAL;
+    if (nstripes == 0)
+        return 0;
+    /* host entry point: device buffers go to _device (locate_host looks at
+     * the fragments and loc before it writes) */
+    if (ecd_ptr_device(out) >= 0)
+        return -EINVAL;
+    rc = locate_host(list, nstripes, avail_mask, frags, loc, &bad, 0);
+    if (rc)
+        return rc;
+    /* a run of stripes that share a decode mask is one combine; the inverses
+     * come from the list's matrix cache */
+    k = list->columns;
+    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+    d.k = k;
+    d.rows = k;
+    d.npatterns = 1;
+    d.pat_bytes = k + k * k;
+    d.in_stride = EC_METHOD_CHUNK_SIZE;
+    d.out_stride = (uint64_t)k * EC_METHOD_CHUNK_SIZE;
+    for (t = 0; t < nstripes; t = t1) {
+        mask = checked_mask(&s, loc[t]);
+        for (t1 = t; t1 < nstripes && checked_mask(&s, loc[t1]) == mask; t1++)
+            many += loc[t1] == EC_MI355X_LOCATE_MANY;
+        if (mask != cur) {
+            rc = mask_pattern(list, mask, d.pat);
+            if (rc)
+                return rc;
+            cur = mask;
+        }
+        d.nstripes = t1 - t;
+        for (b = 0; b < list->rows; b++)
+            d.in_base[b] = (mask >> b) & 1 ? (const uint8_t *)frags[b] + t * EC_METHOD_CHUNK_SIZE
+                                           : NULL;
+        for (r = 0; r < k; r++)
+            d.out_base[r] = (uint8_t *)out + (t * k + r) * EC_METHOD_CHUNK_SIZE;
+        rc = ecc_combine(CTX(list)->isa, &d);
+        if (rc)
+            return rc;
+    }
+    if (nbad)
+        *nbad = bad;
+    if (nmany)
+        *nmany = many;
+    return 0;
+}
+
+static int32_t
+ecm_decode_checked_device_impl(ec_matrix_list_t *list, int device, void *stream,
+                               uint64_t nstripes, uintptr_t avail_mask,
+                               const void *const *frags, void *out, uint32_t *loc)
+{
+    ecm_locate_sets_t s;
+    ecd_combine_desc_t d;
+    uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ginv[ECM_MAX_K];
+    uint8_t pat[ECM_MAX_K + ECM_MAX_K * ECM_MAX_K];
+    uint32_t p, q;
+    int rc;
+
+    rc = locate_args(list, avail_mask, frags, loc, &s);
+    if (rc)
+        return rc;
+    if (!out)
+        return -EINVAL;
+    if (nstripes == 0)
+        return 0;
+    /* device entry point: every buffer lives on `device` */
+    if (device < 0)
+        return -EINVAL;
+    for (p = 0; p < list->columns; p++)
+        if (ecd_ptr_device(s.in[p]) != device)
+            return -EINVAL;
+    for (p = 0; p < s.nr; p++)
+        if (ecd_ptr_device(s.check[p]) != device)
+            return -EINVAL;
+    if (ecd_ptr_device(loc) != device || ecd_ptr_device(out) != device)
+        return -EINVAL;
+    if (!ecd_decode_checked)
+        return -ENODEV;
+    rc = locate_tables(list, &s, &d, ratio);
+    if (rc == 0)
+        rc = mask_pattern(list, s.bmask, pat);
+    if (rc)
+        return rc;
+    /* 1 / G[0][p]: the error of basis position p from the first syndrome */
+    for (p = 0; p < d.k; p++) {
+        q = ec_method_gf_div(1, d.pat[d.k + p]);
+        if (q == 0 || q >= EC_GF_SIZE)
+            return -EINVAL;
+        ginv[p] = (uint8_t)q;
+    }
+    d.nstripes = nstripes;
+    for (p = 0; p < d.k; p++)
+        d.in_base[p] = s.in[p];
+    return ecd_decode_checked(device, stream, &d, s.check, s.cb, s.bb, ratio, pat + d.k, ginv, out,
+                              loc);
+}
+
 /* ------------------------------------------- repairing the named chunks */
 
 /* Weak like ecd_locate: without the symbol ec_method_repair_device is
@@ -3911,6 +4042,28 @@ ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream, uint64
     return ecm_ret("ec_method_locate_device", seq,
                    ecm_locate_device_impl(list, device, stream, nstripes, avail_mask, frags,
                                           loc));
+}
+
+int32_t
+ec_method_decode_checked(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                         const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
+                         uint64_t *nmany)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_decode_checked", seq,
+                   ecm_decode_checked_impl(list, nstripes, avail_mask, frags, out, loc, nbad,
+                                           nmany));
+}
+
+int32_t
+ec_method_decode_checked_device(ec_matrix_list_t *list, int device, void *stream,
+                                uint64_t nstripes, uintptr_t avail_mask,
+                                const void *const *frags, void *out, uint32_t *loc)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_decode_checked_device", seq,
+                   ecm_decode_checked_device_impl(list, device, stream, nstripes, avail_mask,
+                                                  frags, out, loc));
 }
 
 int32_t

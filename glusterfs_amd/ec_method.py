@@ -57,6 +57,7 @@ EXPORTS = (
     "ec_method_repair", "ec_method_repair_device",
     "ec_method_locate2", "ec_method_locate2_device",
     "ec_method_repair2", "ec_method_repair2_device",
+    "ec_method_decode_checked", "ec_method_decode_checked_device",
 )
 
 
@@ -166,6 +167,9 @@ def _load():
         "ec_method_locate_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_locate2": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64)]),
         "ec_method_locate2_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
+        "ec_method_decode_checked": (i32, [P, u64, up, vp, vp, vp, ctypes.POINTER(u64),
+                                           ctypes.POINTER(u64)]),
+        "ec_method_decode_checked_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp, vp]),
         "ec_method_repair": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64),
                                    ctypes.POINTER(u64)]),
         "ec_method_repair_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
@@ -560,6 +564,20 @@ class ECMatrixList:
                "ec_method_locate")
         return nbad.value
 
+    def decode_checked(self, nstripes, avail_mask, frags, out, loc):
+        """ec_method_decode_checked: a read that checks and corrects.  `frags`
+        and `loc` as for locate; `out` (nstripes * k * 512 bytes) gets the
+        decode of the k lowest bricks of avail_mask, around the one brick
+        `loc` names for a stripe, if any.  Returns (nbad, nmany): the stripes
+        with a non-zero entry, and those of them that are
+        EC_MI355X_LOCATE_MANY (to be treated as -EIO)."""
+        nbad, nmany = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib.ec_method_decode_checked(ctypes.byref(self._list), nstripes, avail_mask,
+                                            _ptr_array(frags), addr(out), addr(loc),
+                                            ctypes.byref(nbad), ctypes.byref(nmany)),
+               "ec_method_decode_checked")
+        return nbad.value, nmany.value
+
     def locate2(self, nstripes, avail_mask, frags, loc):
         """ec_method_locate2: which one or two bricks' chunks are wrong?  As
         locate, with k + 4 bricks in avail_mask; `loc` gets 0, the bits of the
@@ -641,6 +659,13 @@ class ECMatrixList:
         return _check(lib.ec_method_locate_device(ctypes.byref(self._list), device, stream,
                                                   nstripes, avail_mask, _ptr_array(frags),
                                                   addr(loc)), "ec_method_locate_device")
+
+    def decode_checked_device(self, device, stream, nstripes, avail_mask, frags, out, loc):
+        """ec_method_decode_checked_device: the same on device buffers (`out`
+        and `loc` too), queued on `stream`; nothing is counted."""
+        return _check(lib.ec_method_decode_checked_device(
+            ctypes.byref(self._list), device, stream, nstripes, avail_mask, _ptr_array(frags),
+            addr(out), addr(loc)), "ec_method_decode_checked_device")
 
     def locate2_device(self, device, stream, nstripes, avail_mask, frags, loc):
         """ec_method_locate2_device: the same on device buffers (`loc` too),

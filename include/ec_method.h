@@ -244,6 +244,57 @@ int32_t ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream
                                 uint64_t nstripes, uintptr_t avail_mask,
                                 const void *const *frags, uint32_t *loc);
 
+/* A read that checks and corrects: ec_method_decode and ec_method_locate in
+ * one pass over the fragments.  ec_method_decode takes exactly k fragments
+ * and trusts them, so one silently damaged chunk comes back as k*512 bytes of
+ * wrong data with return code 0; this call reads the a >= k + 2 fragments at
+ * hand, names the bad brick per stripe and decodes around it.  frags,
+ * avail_mask and loc as for ec_method_locate; out receives nstripes*k*512
+ * bytes, stripe t at out + t*k*512: the layout of ec_method_decode_device's
+ * out, and like it the device variant takes out at any byte alignment (loc
+ * wants 4).
+ *
+ * Let B be the k lowest bricks of avail_mask and B_i the k lowest bricks of
+ * avail_mask other than i (ec_method_repair's B_i).  loc[t] is exactly what
+ * ec_method_locate gives on the same arguments, every loc[0..nstripes)
+ * written, and stripe t of out is, from the stored chunks,
+ *   loc[t] == 0                      ec_method_decode with mask B (the chunks
+ *                                    are consistent: any k give the same);
+ *   loc[t] == 1u << i                ec_method_decode with mask B_i.  For a
+ *                                    check brick B_i = B and the bad chunk
+ *                                    changes nothing; for a basis brick the
+ *                                    damaged chunk is not used;
+ *   loc[t] == EC_MI355X_LOCATE_MANY  ec_method_decode with mask B as stored:
+ *                                    defined bytes, but the caller must treat
+ *                                    the stripe as -EIO.
+ * So wherever at most one chunk of a stripe is damaged, out is the data the
+ * fragments were encoded from.  The a - k == 2 caveat of ec_method_locate
+ * carries over: two damaged chunks can imitate one, and out is then what the
+ * code implies.  Nothing in frags is written, and nothing past
+ * out + nstripes*k*512.
+ *
+ * *nbad (host variant, may be NULL) = stripes with loc[t] != 0; *nmany (may
+ * be NULL) = stripes with loc[t] == EC_MI355X_LOCATE_MANY.  The device
+ * variant counts nothing: the caller reduces loc[].
+ *
+ * -EINVAL: as ec_method_locate, and a NULL out (the device variant wants out
+ * on `device` too).  nstripes == 0 returns 0 after these checks and writes
+ * nothing.
+ *
+ * Like ec_method_locate, the host variant runs on the calling thread's CPU
+ * engine whatever the volume's engine is and leaves ec_method_stats_t, the
+ * router and the run-time compiler alone; the device variant is asynchronous
+ * on `stream` with no host synchronisation (inv(B) and every other table
+ * travel in the kernel arguments), reads a and writes k chunks per stripe,
+ * pre-zeroes nothing, uses no global atomics and writes each loc[t] by one
+ * plain store (-ENODEV where the device layer lacks it). */
+int32_t ec_method_decode_checked(ec_matrix_list_t *list, uint64_t nstripes,
+                                 uintptr_t avail_mask, const void *const *frags, void *out,
+                                 uint32_t *loc, uint64_t *nbad, uint64_t *nmany);
+int32_t ec_method_decode_checked_device(ec_matrix_list_t *list, int device, void *stream,
+                                        uint64_t nstripes, uintptr_t avail_mask,
+                                        const void *const *frags, void *out, uint32_t *loc);
+
 /* Locating up to two damaged bricks.  Arguments, buffer rules, asynchrony
  * and error codes are ec_method_locate's, except that avail_mask must name
  * a >= k + 4 bricks: fewer bits are -EINVAL (so every call on a 2+1 or 4+2
