@@ -104,6 +104,17 @@ int ecd_decode_checked(int device, void *stream, const ecd_combine_desc_t *d,
 int ecd_locate2(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc);
+/* A read that corrects up to two chunks (ec_method_decode_checked2_device):
+ * the arguments of ecd_locate2 with basis_brick ascending, then inv[j * k +
+ * p] as for ecd_decode_checked and ginv[r * k + p] = 1 / G[r][p] for rows 0
+ * and 1.  loc[t] is ecd_locate2's.  out (as for ecd_decode_checked) gets the
+ * decode of stripe t's k inputs, after the one or two inputs loc[t] names, if
+ * any, have been corrected to agree with the bricks it does not name. */
+int ecd_decode_checked2(int device, void *stream, const ecd_combine_desc_t *d,
+                        const void *const *check, const uint8_t *check_brick,
+                        const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *ratio1,
+                        const uint8_t *pair_inv, const uint8_t *inv, const uint8_t *ginv,
+                        void *out, uint32_t *loc);
 /* Repairing what locate named (ec_method_repair_device): frags[] is indexed
  * by brick and read for the bits of avail (no bit at or above 31); bset is
  * the k + 1 lowest bricks of avail, ascending: the basis B of ecd_locate and

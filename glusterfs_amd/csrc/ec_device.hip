@@ -1668,6 +1668,21 @@ int ecd_locate2(int device, void *stream, const ecd_combine_desc_t *d, const voi
                         pair_inv, loc);
 }
 
+int ecd_decode_checked2(int device, void *stream, const ecd_combine_desc_t *d,
+                        const void *const *check, const uint8_t *check_brick,
+                        const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *ratio1,
+                        const uint8_t *pair_inv, const uint8_t *inv, const uint8_t *ginv,
+                        void *out, uint32_t *loc)
+{
+    if (ecd_device_count() <= device || device < 0)
+        return -ENODEV;
+    DeviceGuard dg;
+    clear_stale_error();
+    HIPCHK(hipSetDevice(g_dev_ids[device]));
+    return ecdk_decode_checked2(pick_stream(stream), d, check, check_brick, basis_brick, ratio,
+                                ratio1, pair_inv, inv, ginv, out, loc);
+}
+
 int ecd_repair(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
                uint32_t avail, const uint8_t *bset, const uint8_t *coef, const uint32_t *loc)
 {

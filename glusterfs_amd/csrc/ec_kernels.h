@@ -34,6 +34,12 @@ int ecdk_decode_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *
 int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                  const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                  const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc);
+/* the decode corrected around up to two chunks of ecd_decode_checked2
+ * (ec_decode_checked2_n) */
+int ecdk_decode_checked2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                         const uint8_t *check_brick, const uint8_t *basis_brick,
+                         const uint8_t *ratio, const uint8_t *ratio1, const uint8_t *pair_inv,
+                         const uint8_t *inv, const uint8_t *ginv, void *out, uint32_t *loc);
 /* rewriting the chunks loc[] names, of ecd_repair (ec_repair_n) */
 int ecdk_repair(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
                 const uint8_t *bset, const uint8_t *coef, const uint32_t *loc);

@@ -26,6 +26,9 @@
  *            scan, a pair rebuilt from the syndromes and locate2's tables
  *   checked  a read that checks and corrects: ec_decode_checked_n, locate's
  *   decode   tile, the named basis chunk corrected in LDS, one dense decode
+ *   checked2 the same read around up to two chunks: ec_decode_checked2_n,
+ *   decode   locate2's three phases, at most four products XORed into the
+ *            named basis chunks in LDS, one dense decode
  *   stores   non-temporal on every device-path kernel except the 2+1 / 4+2
  *            register encoders (profiles/kbench_r01_nts.log)
  *   staging  LDS-DMA loads non-temporal for calls whose input exceeds the
@@ -1149,22 +1152,17 @@ int launch_locate2_k(hipStream_t s, const Locate2Args &a)
 
 } // namespace
 
-/* As ecdk_locate, with at least four rows.  ratio1: (rows - 2) x k bytes,
- * coefficient of row r over that of row 1, for r >= 2; pair_inv: 4 bytes
- * {a, b, c, d} per basis pair p < q in lexicographic order, the inverse of
- * rows 0 and 1 of columns p and q (ec_kernels_impl.h, Locate2Args).  Every
- * table travels in the kernel arguments: nothing is uploaded. */
-int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
-                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
-                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc)
+/* The arguments of ec_locate2_n from what ecdk_locate2 is given: pack_locate,
+ * then ratio1, the pairs' inverses and their positions. */
+static int pack_locate2(const ecd_combine_desc_t *d, const void *const *check,
+                        const uint8_t *check_brick, const uint8_t *basis_brick,
+                        const uint8_t *ratio, const uint8_t *ratio1, const uint8_t *pair_inv,
+                        uint32_t *loc, Locate2Args &a, uintptr_t *align)
 {
-    static_assert(sizeof(Locate2Args) <= 2048, "the tables must fit the kernel arguments");
-    Locate2Args a;
-    uintptr_t o = 0;
     if (!ratio1 || !pair_inv || d->rows < 4)
         return -EINVAL;
     memset(&a, 0, sizeof(a));
-    if (int rc = pack_locate(d, check, check_brick, basis_brick, ratio, loc, a.l, &o))
+    if (int rc = pack_locate(d, check, check_brick, basis_brick, ratio, loc, a.l, align))
         return rc;
     const u32 k = a.l.k, kw = a.l.kw;
     for (u32 r = 2; r < a.l.rows; ++r)
@@ -1177,9 +1175,94 @@ int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *
             a.ppq[i >> 2] |= (p << 4 | q) << ((i & 3u) * 8u);
         }
     a.npairs = i;
+    return 0;
+}
+
+/* As ecdk_locate, with at least four rows.  ratio1: (rows - 2) x k bytes,
+ * coefficient of row r over that of row 1, for r >= 2; pair_inv: 4 bytes
+ * {a, b, c, d} per basis pair p < q in lexicographic order, the inverse of
+ * rows 0 and 1 of columns p and q (ec_kernels_impl.h, Locate2Args).  Every
+ * table travels in the kernel arguments: nothing is uploaded. */
+int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
+                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc)
+{
+    static_assert(sizeof(Locate2Args) <= 2048, "the tables must fit the kernel arguments");
+    Locate2Args a;
+    uintptr_t o = 0;
+    if (int rc = pack_locate2(d, check, check_brick, basis_brick, ratio, ratio1, pair_inv, loc, a,
+                              &o))
+        return rc;
     /* the staging policy of ecdk_locate, by the bytes the call reads */
-    const bool nt = nt_staging(a.l.nstripes * (k + a.l.rows) * ECD_CHUNK) && (o & 15u) == 0;
+    const bool nt = nt_staging(a.l.nstripes * (a.l.k + a.l.rows) * ECD_CHUNK) && (o & 15u) == 0;
     return nt ? launch_locate2_k<kLdsDmaNT>(s, a) : launch_locate2_k<kLdsDmaDefault>(s, a);
+}
+
+/* ------------------------------------- a read that corrects up to two chunks */
+
+namespace {
+
+template <int K, int NW, int LA>
+int launch_decode_checked2(hipStream_t s, const DecodeChecked2Args &a)
+{
+    const uint64_t g = (a.l2.l.nstripes + 3) / 4;
+    if (g == 0)
+        return 0;
+    if (g > 0x7fffffffull)
+        return -EINVAL;
+    /* the tile and the words of ec_locate2_n: at most 62 KiB + 48 */
+    const size_t lds = locate2_n_lds(a.l2.l.k + a.l2.l.rows);
+    hipLaunchKernelGGL((ec_decode_checked2_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
+    return launch_ok("launch_decode_checked2");
+}
+
+/* the buckets and wave counts of launch_locate2_k */
+template <int LA>
+int launch_decode_checked2_k(hipStream_t s, const DecodeChecked2Args &a)
+{
+    if (a.l2.l.k <= 4)
+        return launch_decode_checked2<4, 4, LA>(s, a);
+    if (a.l2.l.k <= 8)
+        return a.l2.l.nstripes <= (1u << 17) ? launch_decode_checked2<8, 8, LA>(s, a)
+                                             : launch_decode_checked2<8, 4, LA>(s, a);
+    return launch_decode_checked2<16, 8, LA>(s, a);
+}
+
+} // namespace
+
+/* As ecdk_locate2, then inv: k x k bytes, the decode matrix of the basis (row
+ * j gives output chunk j); ginv: 2 x k bytes, 1 / coefficient of row 0, then
+ * of row 1; out: nstripes * k * 512 device bytes at any alignment.  Every
+ * table travels in the kernel arguments: nothing is uploaded. */
+int ecdk_decode_checked2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                         const uint8_t *check_brick, const uint8_t *basis_brick,
+                         const uint8_t *ratio, const uint8_t *ratio1, const uint8_t *pair_inv,
+                         const uint8_t *inv, const uint8_t *ginv, void *out, uint32_t *loc)
+{
+    static_assert(sizeof(DecodeChecked2Args) <= 2048, "the tables must fit the kernel arguments");
+    DecodeChecked2Args a;
+    uintptr_t o = 0;
+    if (!inv || !ginv || !out)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    if (int rc = pack_locate2(d, check, check_brick, basis_brick, ratio, ratio1, pair_inv, loc,
+                              a.l2, &o))
+        return rc;
+    const u32 k = a.l2.l.k, kw = a.l2.l.kw;
+    a.out = static_cast<uint8_t *>(out);
+    for (u32 p = 0; p < k; ++p) {
+        if (ginv[p] == 0 || ginv[k + p] == 0)
+            return -EINVAL;
+        a.bmask |= 1u << basis_brick[p];
+        a.ginv[p >> 2] |= (u32)ginv[p] << ((p & 3u) * 8u);
+        a.ginv[ECD_MAX_K / 4 + (p >> 2)] |= (u32)ginv[k + p] << ((p & 3u) * 8u);
+        for (u32 j = 0; j < k; ++j)
+            a.inv[j * kw + (p >> 2)] |= (u32)inv[j * k + p] << ((p & 3u) * 8u);
+    }
+    /* the staging policy of ecdk_locate2, by the bytes the call reads */
+    const bool nt = nt_staging(a.l2.l.nstripes * (k + a.l2.l.rows) * ECD_CHUNK) && (o & 15u) == 0;
+    return nt ? launch_decode_checked2_k<kLdsDmaNT>(s, a)
+              : launch_decode_checked2_k<kLdsDmaDefault>(s, a);
 }
 
 /* ------------------------------------------- repairing the named chunks */

@@ -2169,6 +2169,313 @@ constexpr size_t locate2_n_lds(u32 inputs)
     return (size_t)inputs * 4 * ECD_CHUNK + 12 * sizeof(u32);
 }
 
+/* ------------------------------------- a read that corrects up to two chunks */
+
+/* Kernel arguments of ec_decode_checked2_n: Locate2Args, then the decoded
+ * output (stripe t at out + t * k * 512, any byte alignment), B as a brick
+ * mask, inv(B) laid out like the coefficients (row j at word j * kw) and the
+ * k bytes 1 / G[0][p] (ginv[0 ..]) and 1 / G[1][p] (ginv[ECD_MAX_K / 4 ..]).
+ * 2,016 bytes in all. */
+struct DecodeChecked2Args {
+    Locate2Args l2;
+    uint8_t *out;
+    u32 bmask, pad;
+    u32 inv[ECD_MAX_K * (ECD_MAX_K / 4)];
+    u32 ginv[2 * (ECD_MAX_K / 4)];
+};
+
+/* the word of ec_locate2_n's last statement, from a stripe's three words */
+__device__ __forceinline__ u32 locate2_word(u32 f, u32 b, u32 w)
+{
+    const u32 nz = __builtin_popcount(f);
+    return nz <= 1 ? f : b ? b : nz == 2 ? f
+           : __builtin_popcount(w) == 2 ? w : kLocateMany;
+}
+
+/* ec_method_decode_checked2_device: decode the k lowest bricks and, in the
+ * same pass, check them against the others and correct up to two bad chunks.
+ * Phases 1 to 3 are ec_locate2_n's, statement for statement: the tile, the
+ * syndromes left in the check chunks' LDS slots, the three words per stripe.
+ * Its two early returns are ifs here: a clean tile skips phases 2 and 3 and
+ * the correction, a tile without an open stripe skips phase 3.  Words phase 3
+ * did not touch are zero, so one expression (locate2_word) gives the final
+ * word W of a stripe on every path.
+ *
+ * The correction, for a stripe whose W names one or two basis positions (the
+ * a - |S| other chunks lie on one codeword; its basis part is the stored basis
+ * with an error XORed into each named position):
+ *   p alone, or p and a check row c   e_p = s_ref / G[ref][p], ref = 0, or 1
+ *                                     when c is row 0 (rows >= 4: row 1 is
+ *                                     intact then);
+ *   p < q                             e_p = a s_0 ^ b s_1, e_q = c s_0 ^ d s_1,
+ *                                     {a, b, c, d} = pinv of the pair.
+ * That is at most four terms (coefficient, s_0 or s_1, slot), one loop around
+ * one multiply site.  The jump-table multiply wants a wave-uniform
+ * coefficient: the tile's four stripes go one per wave item, each on its own
+ * 16 lanes.  MANY stripes, check-only stripes and stripes past nstripes
+ * (W = 0) are left alone.  After it one dense decode with inv(B) gives what
+ * inv(B_S) would give from the undamaged chunks, as in ec_decode_checked_n.
+ * No barrier sits in a loop, and every decision around one is read from LDS
+ * after a barrier, so the whole block takes it together. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_decode_checked2_n(const DecodeChecked2Args a)
+{
+    constexpr u32 T = 4;
+    static_assert(NW >= (int)T, "a wave per stripe of the tile");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 tid = threadIdx.x;
+    const u32 k = a.l2.l.k, kw = a.l2.l.kw, rows = a.l2.l.rows, ni = k + rows;
+    const uint64_t t0 = (uint64_t)blockIdx.x * T;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    /* flags[s], flags[T + s], flags[2T + s]: as in ec_locate2_n */
+    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
+    if (tid < 3 * T)
+        flags[tid] = 0;
+    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        return a.l2.l.in[p] + st * ECD_CHUNK;
+    }, ni, t0, a.l2.l.nstripes, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    uint8_t *col = lds + cs * 64u + cc * 4u;
+    const bool live = t0 + cs < a.l2.l.nstripes;
+    for (u32 r = wave; r < rows; r += NW) {
+        const u32 rw = kw * r;
+        const u32 w0 = a.l2.l.coef[rw];
+        const u32 w1 = K > 4 ? a.l2.l.coef[rw + 1] : 0u;
+        const u32 w2 = K > 8 ? a.l2.l.coef[rw + 2] : 0u;
+        const u32 w3 = K > 12 ? a.l2.l.coef[rw + 3] : 0u;
+        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
+        u32 acc[8][1], y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            acc[b][0] = 0;
+#pragma unroll 1
+        for (u32 p = 0; p < k; ++p) {
+            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+            cl = (cl >> 8) | (ch << 56);
+            ch >>= 8;
+            if (c == 0)
+                continue;
+            const uint8_t *src = col + p * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+            ecgf::mul_xor_jt<1>(c, acc, y);
+        }
+        /* the syndrome replaces the stored chunk in LDS */
+        uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
+        u32 d = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (T * 64u));
+            const u32 s = acc[b][0] ^ *w;
+            *w = s;
+            d |= s;
+        }
+        const uint64_t vote = __ballot(live && d != 0);
+        const u32 brick = __builtin_amdgcn_readfirstlane((a.l2.l.cbrick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
+        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
+            atomicOr(&flags[cs], 1u << brick);
+    }
+    __syncthreads();
+    const uint8_t *syn = col + k * (T * ECD_CHUNK);
+    const u32 any = __builtin_amdgcn_readfirstlane(flags[0] | flags[1] | flags[2] | flags[3]);
+    if (any != 0) {
+        /* a stripe with two or more non-zero rows looks for its basis position
+         * (stripes past nstripes have no flag) */
+        const u32 mine = flags[cs];
+        const bool open = (mine & (mine - 1u)) != 0;
+        for (u32 p = wave; p < k; p += NW) {
+            u32 y[8][1];
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(syn + (u32)b * (T * 64u));
+            u32 d = 0;
+#pragma unroll 1
+            for (u32 r = 1; r < rows; ++r) {
+                const u32 q = __builtin_amdgcn_readfirstlane(
+                    (a.l2.l.ratio[(r - 1) * kw + (p >> 2)] >> ((p & 3u) * 8u)) & 0xFFu);
+                u32 acc[8][1];
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    acc[b][0] = 0;
+                if (q != 0)
+                    ecgf::mul_xor_jt<1>(q, acc, y);
+                const uint8_t *sr = syn + r * (T * ECD_CHUNK);
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
+            }
+            const uint64_t vote = __ballot(d != 0);
+            const u32 brick = __builtin_amdgcn_readfirstlane((a.l2.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
+            if (cc == 0 && open && ((vote >> (cs * 16u)) & 0xFFFFu) == 0)
+                atomicOr(&flags[T + cs], 1u << brick);
+        }
+        __syncthreads();
+        /* open for a pair: three or more non-zero rows, no single position */
+        u32 need = 0;
+#pragma unroll
+        for (u32 s = 0; s < T; ++s)
+            need |= (u32)(__builtin_popcount(flags[s]) >= 3 && flags[T + s] == 0);
+        if (__builtin_amdgcn_readfirstlane(need) != 0) {
+            const bool open2 = __builtin_popcount(mine) >= 3 && flags[T + cs] == 0;
+            const u32 nitems = 2u * k + a.l2.npairs;
+            for (u32 it = wave; it < nitems; it += NW) {
+                /* wave-uniform: a basis pair (p, q), or position p against row ref */
+                const bool pair = it >= 2u * k;
+                const u32 pi = pair ? it - 2u * k : 0u;
+                const u32 pq = __builtin_amdgcn_readfirstlane((a.l2.ppq[pi >> 2] >> ((pi & 3u) * 8u)) & 0xFFu);
+                const u32 inv = __builtin_amdgcn_readfirstlane(a.l2.pinv[pi]);
+                const u32 ref = pair ? 0u : it >= k ? 1u : 0u;
+                const u32 p = pair ? pq >> 4 : it - ref * k;
+                const u32 q = pq & 15u;
+                u32 ep[8][1], eq[8][1];
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    ep[b][0] = eq[b][0] = 0;
+                u32 failed = 0;         /* rows of this lane's stripe that do not fit */
+#pragma unroll 1
+                for (u32 st = pair ? 0u : ref + 1u; st < rows; ++st) {
+                    const bool solve = pair && st < 2u;
+                    u32 acc[8][1], y[8][1];
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        acc[b][0] = 0;
+#pragma unroll 1
+                    for (u32 j = 0; j < (pair ? 2u : 1u); ++j) {
+                        u32 c;
+                        if (!pair || solve) {
+                            /* from LDS: s_ref, or s_0 and s_1 */
+                            const u32 *tab = ref ? a.l2.ratio1 : a.l2.l.ratio;
+                            const u32 ri = pair ? 0u : (st - 1u - ref) * kw + (p >> 2);
+                            c = pair ? (inv >> ((2u * st + j) * 8u)) & 0xFFu
+                                     : (tab[ri] >> ((p & 3u) * 8u)) & 0xFFu;
+                            const uint8_t *src = syn + (pair ? j : ref) * (T * ECD_CHUNK);
+#pragma unroll
+                            for (int b = 0; b < 8; ++b)
+                                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+                        } else {
+                            const u32 x = j ? q : p;
+                            c = (a.l2.l.coef[st * kw + (x >> 2)] >> ((x & 3u) * 8u)) & 0xFFu;
+#pragma unroll
+                            for (int b = 0; b < 8; ++b)
+                                y[b][0] = j ? eq[b][0] : ep[b][0];
+                        }
+                        c = __builtin_amdgcn_readfirstlane(c);
+                        if (c != 0)
+                            ecgf::mul_xor_jt<1>(c, acc, y);
+                    }
+                    if (solve) {
+#pragma unroll
+                        for (int b = 0; b < 8; ++b) {
+                            if (st == 0)
+                                ep[b][0] = acc[b][0];
+                            else
+                                eq[b][0] = acc[b][0];
+                        }
+                        continue;
+                    }
+                    const uint8_t *sr = syn + st * (T * ECD_CHUNK);
+                    u32 d = 0;
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
+                    const uint64_t vote = __ballot(d != 0);
+                    if (((vote >> (cs * 16u)) & 0xFFFFu) != 0)
+                        failed |= 1u << st;
+                }
+                /* (p, ref 0): the one failing row is the pair's check brick;
+                 * otherwise nothing may fail, and the second brick is row 0's, or q's */
+                const bool one = !pair && ref == 0;
+                const bool pass = one ? __builtin_popcount(failed) == 1 : failed == 0;
+                if (cc == 0 && open2 && pass) {
+                    const u32 cr = one ? (u32)__builtin_ctz(failed) : 0u;
+                    const u32 b0 = (a.l2.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu;
+                    const u32 b1 = pair ? (a.l2.l.bbrick[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu
+                                        : (a.l2.l.cbrick[cr >> 2] >> ((cr & 3u) * 8u)) & 0xFFu;
+                    atomicOr(&flags[2 * T + cs], (1u << b0) | (1u << b1));
+                }
+            }
+            __syncthreads();
+        }
+        /* stripe s of the tile, on lanes 16 s .. 16 s + 15 of one wave: its
+         * words are final.  W names nb bricks of B: none (clean, check bricks
+         * only, MANY, past nstripes) leaves the stripe alone; one is position
+         * p, with s_0, or with s_1 when W's other bit is the brick of check
+         * row 0; two are p < q with the four bytes of their pinv. */
+        for (u32 s = wave; s < T; s += NW) {
+            const u32 w = __builtin_amdgcn_readfirstlane(
+                locate2_word(flags[s], flags[T + s], flags[2 * T + s]));
+            const u32 wb = w & a.bmask;
+            if (wb == 0)
+                continue;
+            const bool two = (wb & (wb - 1u)) != 0;
+            const u32 p = (u32)__builtin_popcount(a.bmask & ((wb & (0u - wb)) - 1u));
+            const u32 q = (u32)__builtin_popcount(a.bmask & ((wb & (wb - 1u)) - 1u));
+            const u32 ref = !two && (w ^ wb) == 1u << (a.l2.l.cbrick[0] & 0xFFu) ? 1u : 0u;
+            const u32 gi = ref * (ECD_MAX_K / 4) + (p >> 2);
+            const u32 cw = two ? a.l2.pinv[p * (2u * k - p - 1u) / 2u + q - p - 1u]
+                               : (a.ginv[gi] >> ((p & 3u) * 8u)) & 0xFFu;
+            const u32 nterms = two ? 4u : 1u;
+#pragma unroll 1
+            for (u32 i = 0; i < nterms; ++i) {
+                const u32 c = __builtin_amdgcn_readfirstlane((cw >> (i * 8u)) & 0xFFu);
+                if (c == 0)
+                    continue;
+                const uint8_t *src = syn + (two ? i & 1u : ref) * (T * ECD_CHUNK);
+                u32 acc[8][1], y[8][1];
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    acc[b][0] = 0;
+                    y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+                }
+                ecgf::mul_xor_jt<1>(c, acc, y);
+                if (cs == s) {
+                    uint8_t *x = col + (i < 2u ? p : q) * (T * ECD_CHUNK);
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+                        *reinterpret_cast<u32 *>(x + (u32)b * (T * 64u)) ^= acc[b][0];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    /* the decode of the (corrected) basis chunks */
+    uint8_t *o = a.out + (t0 + cs) * ((uint64_t)k * ECD_CHUNK) + cc * 4u;
+    for (u32 j = wave; j < k; j += NW) {
+        const u32 rw = kw * j;
+        const u32 w0 = a.inv[rw];
+        const u32 w1 = K > 4 ? a.inv[rw + 1] : 0u;
+        const u32 w2 = K > 8 ? a.inv[rw + 2] : 0u;
+        const u32 w3 = K > 12 ? a.inv[rw + 3] : 0u;
+        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
+        u32 acc[8][1], y[8][1];
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            acc[b][0] = 0;
+#pragma unroll 1
+        for (u32 p = 0; p < k; ++p) {
+            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+            cl = (cl >> 8) | (ch << 56);
+            ch >>= 8;
+            if (c == 0)
+                continue;
+            const uint8_t *src = col + p * (T * ECD_CHUNK);
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+            ecgf::mul_xor_jt<1>(c, acc, y);
+        }
+        if (live)
+            store_chunk<1, true>(o + j * ECD_CHUNK, acc);
+    }
+    if (tid < T && t0 + tid < a.l2.l.nstripes)
+        a.l2.l.loc[t0 + tid] = locate2_word(flags[tid], flags[T + tid], flags[2 * T + tid]);
+}
+
 /* ------------------------------------------- repairing the named chunks */
 
 /* Kernel arguments of ec_repair_n.  frag[] is indexed by brick (null outside

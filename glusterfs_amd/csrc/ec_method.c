@@ -3239,25 +3239,32 @@ ecm_locate2_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64
 
 /* ------------------------------------------- a read that checks and corrects */
 
-/* Weak like ecd_locate: without the symbol ec_method_decode_checked_device is
- * -ENODEV. */
+/* Weak like ecd_locate: without the symbols ec_method_decode_checked_device
+ * and ec_method_decode_checked2_device are -ENODEV. */
 extern __typeof__(ecd_decode_checked) ecd_decode_checked __attribute__((weak));
+extern __typeof__(ecd_decode_checked2) ecd_decode_checked2 __attribute__((weak));
 
-/* The mask stripe t is decoded with: B, or B_i = B without i and with c0 (the
- * lowest check brick) when loc[t] names basis brick i.  MANY is bit 31 and no
- * mask has a bit there. */
+/* The mask stripe t is decoded with: B, or B_S = B without the basis bricks
+ * loc[t] names and with as many of the lowest check bricks it does not name
+ * (for one basis brick i that is B_i: B without i and with c0).  MANY is bit
+ * 31 and no mask has a bit there. */
 static uintptr_t
 checked_mask(const ecm_locate_sets_t *s, uint32_t w)
 {
-    if (((uintptr_t)w & s->bmask) == 0)
-        return s->bmask;
-    return (s->bmask & ~(uintptr_t)w) | (s->rmask & (~s->rmask + 1));
+    uintptr_t named = (uintptr_t)w & s->bmask, spare = s->rmask & ~(uintptr_t)w;
+    uintptr_t mask = s->bmask & ~named;
+
+    for (; named; named &= named - 1, spare &= spare - 1)
+        mask |= spare & (~spare + 1);
+    return mask;
 }
 
+/* Both host calls: `two` = ec_method_decode_checked2 (a >= k + 4, loc[] is
+ * ec_method_locate2's and a pair is decoded around). */
 static int32_t
-ecm_decode_checked_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                        const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
-                        uint64_t *nmany)
+decode_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                    const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
+                    uint64_t *nmany, int two)
 {
     ecm_locate_sets_t s;
     ecd_combine_desc_t d;
@@ -3269,7 +3276,7 @@ ecm_decode_checked_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t ava
     rc = locate_args(list, avail_mask, frags, loc, &s);
     if (rc)
         return rc;
-    if (!out)
+    if (!out || (two && s.nr < 4))
         return -EINVAL;
     if (nstripes == 0)
         return 0;
@@ -3277,7 +3284,7 @@ ecm_decode_checked_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t ava
      * the fragments and loc before it writes) */
     if (ecd_ptr_device(out) >= 0)
         return -EINVAL;
-    rc = locate_host(list, nstripes, avail_mask, frags, loc, &bad, 0);
+    rc = locate_host(list, nstripes, avail_mask, frags, loc, &bad, two);
     if (rc)
         return rc;
     /* a run of stripes that share a decode mask is one combine; the inverses
@@ -3318,21 +3325,39 @@ ecm_decode_checked_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t ava
 }
 
 static int32_t
-ecm_decode_checked_device_impl(ec_matrix_list_t *list, int device, void *stream,
-                               uint64_t nstripes, uintptr_t avail_mask,
-                               const void *const *frags, void *out, uint32_t *loc)
+ecm_decode_checked_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                        const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
+                        uint64_t *nmany)
+{
+    return decode_checked_host(list, nstripes, avail_mask, frags, out, loc, nbad, nmany, 0);
+}
+
+static int32_t
+ecm_decode_checked2_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                         const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
+                         uint64_t *nmany)
+{
+    return decode_checked_host(list, nstripes, avail_mask, frags, out, loc, nbad, nmany, 1);
+}
+
+/* Both device calls: `two` = ec_method_decode_checked2_device. */
+static int32_t
+decode_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                      uintptr_t avail_mask, const void *const *frags, void *out, uint32_t *loc,
+                      int two)
 {
     ecm_locate_sets_t s;
     ecd_combine_desc_t d;
-    uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ginv[ECM_MAX_K];
+    uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ratio1[ECM_MAX_N * ECM_MAX_K], ginv[2 * ECM_MAX_K];
+    uint8_t pinv[ECM_MAX_K * (ECM_MAX_K - 1) / 2 * 4];
     uint8_t pat[ECM_MAX_K + ECM_MAX_K * ECM_MAX_K];
-    uint32_t p, q;
+    uint32_t p, q, r;
     int rc;
 
     rc = locate_args(list, avail_mask, frags, loc, &s);
     if (rc)
         return rc;
-    if (!out)
+    if (!out || (two && s.nr < 4))
         return -EINVAL;
     if (nstripes == 0)
         return 0;
@@ -3347,25 +3372,48 @@ ecm_decode_checked_device_impl(ec_matrix_list_t *list, int device, void *stream,
             return -EINVAL;
     if (ecd_ptr_device(loc) != device || ecd_ptr_device(out) != device)
         return -EINVAL;
-    if (!ecd_decode_checked)
+    if (two ? !ecd_decode_checked2 : !ecd_decode_checked)
         return -ENODEV;
     rc = locate_tables(list, &s, &d, ratio);
+    if (rc == 0 && two)
+        rc = locate2_tables(d.k, s.nr, d.pat + d.k, ratio1, pinv);
     if (rc == 0)
         rc = mask_pattern(list, s.bmask, pat);
     if (rc)
         return rc;
-    /* 1 / G[0][p]: the error of basis position p from the first syndrome */
-    for (p = 0; p < d.k; p++) {
-        q = ec_method_gf_div(1, d.pat[d.k + p]);
-        if (q == 0 || q >= EC_GF_SIZE)
-            return -EINVAL;
-        ginv[p] = (uint8_t)q;
-    }
+    /* 1 / G[0][p]: the error of basis position p from the first syndrome;
+     * with `two` also 1 / G[1][p], for a pair whose check brick is row 0 */
+    for (r = 0; r < (two ? 2u : 1u); r++)
+        for (p = 0; p < d.k; p++) {
+            q = ec_method_gf_div(1, d.pat[d.k + r * d.k + p]);
+            if (q == 0 || q >= EC_GF_SIZE)
+                return -EINVAL;
+            ginv[r * d.k + p] = (uint8_t)q;
+        }
     d.nstripes = nstripes;
     for (p = 0; p < d.k; p++)
         d.in_base[p] = s.in[p];
+    if (two)
+        return ecd_decode_checked2(device, stream, &d, s.check, s.cb, s.bb, ratio, ratio1, pinv,
+                                   pat + d.k, ginv, out, loc);
     return ecd_decode_checked(device, stream, &d, s.check, s.cb, s.bb, ratio, pat + d.k, ginv, out,
                               loc);
+}
+
+static int32_t
+ecm_decode_checked_device_impl(ec_matrix_list_t *list, int device, void *stream,
+                               uint64_t nstripes, uintptr_t avail_mask,
+                               const void *const *frags, void *out, uint32_t *loc)
+{
+    return decode_checked_device(list, device, stream, nstripes, avail_mask, frags, out, loc, 0);
+}
+
+static int32_t
+ecm_decode_checked2_device_impl(ec_matrix_list_t *list, int device, void *stream,
+                                uint64_t nstripes, uintptr_t avail_mask,
+                                const void *const *frags, void *out, uint32_t *loc)
+{
+    return decode_checked_device(list, device, stream, nstripes, avail_mask, frags, out, loc, 1);
 }
 
 /* ------------------------------------------- repairing the named chunks */
@@ -4064,6 +4112,28 @@ ec_method_decode_checked_device(ec_matrix_list_t *list, int device, void *stream
     return ecm_ret("ec_method_decode_checked_device", seq,
                    ecm_decode_checked_device_impl(list, device, stream, nstripes, avail_mask,
                                                   frags, out, loc));
+}
+
+int32_t
+ec_method_decode_checked2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                          const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
+                          uint64_t *nmany)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_decode_checked2", seq,
+                   ecm_decode_checked2_impl(list, nstripes, avail_mask, frags, out, loc, nbad,
+                                            nmany));
+}
+
+int32_t
+ec_method_decode_checked2_device(ec_matrix_list_t *list, int device, void *stream,
+                                 uint64_t nstripes, uintptr_t avail_mask,
+                                 const void *const *frags, void *out, uint32_t *loc)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_decode_checked2_device", seq,
+                   ecm_decode_checked2_device_impl(list, device, stream, nstripes, avail_mask,
+                                                   frags, out, loc));
 }
 
 int32_t

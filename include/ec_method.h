@@ -339,6 +339,56 @@ int32_t ec_method_locate2_device(ec_matrix_list_t *list, int device, void *strea
                                  uint64_t nstripes, uintptr_t avail_mask,
                                  const void *const *frags, uint32_t *loc);
 
+/* A read that corrects two chunks: ec_method_decode_checked with
+ * ec_method_locate2's answer in place of ec_method_locate's.  Arguments,
+ * buffer rules, asynchrony, alignment and error codes are those of
+ * ec_method_decode_checked, except that avail_mask must name a >= k + 4
+ * bricks, as for ec_method_locate2: fewer bits are -EINVAL (so every call on
+ * a 2+1 or 4+2 volume).  out takes any byte alignment on the device, loc
+ * wants 4.  Nothing in frags is written, and nothing past
+ * out + nstripes*k*512.  nstripes == 0 returns 0 after the argument checks
+ * and writes nothing.
+ *
+ * Let B be the k lowest bricks of avail_mask and, for a set S of bricks, B_S
+ * the k lowest bricks of avail_mask not in S.  loc[t] is exactly what
+ * ec_method_locate2 gives on the same arguments, every loc[0..nstripes)
+ * written, and stripe t of out is, from the stored chunks,
+ *   loc[t] == 0                      ec_method_decode with mask B;
+ *   loc[t] == one or two bits, the   ec_method_decode with mask B_S.  For one
+ *             bricks of S            bit this is ec_method_decode_checked's
+ *                                    answer; for two check bricks B_S = B; for
+ *                                    basis + check and basis + basis the
+ *                                    damaged chunks are not used;
+ *   loc[t] == EC_MI355X_LOCATE_MANY  ec_method_decode with mask B as stored:
+ *                                    defined bytes, but the caller must treat
+ *                                    the stripe as -EIO.
+ * What follows:
+ *   - wherever at most two chunks of a stripe are damaged, out is the data
+ *     the fragments were encoded from;
+ *   - wherever ec_method_decode_checked on the same arguments gives 0 or a
+ *     single bit, loc[t] and stripe t of out are byte for byte the same here;
+ *   - the a - k == 4 caveat of ec_method_locate2 carries over: three damaged
+ *     chunks can imitate a pair, and out is then what the code implies.
+ *
+ * *nbad (host variant, may be NULL) = stripes with loc[t] != 0; *nmany (may
+ * be NULL) = stripes with loc[t] == EC_MI355X_LOCATE_MANY.  The device
+ * variant counts nothing: the caller reduces loc[].
+ *
+ * The host variant runs on the calling thread's CPU engine whatever the
+ * volume's engine is, leaves ec_method_stats_t, the router and the run-time
+ * compiler alone, and answers -EINVAL to a device pointer; the device variant
+ * is asynchronous on `stream` with no host synchronisation (inv(B), the
+ * tables of locate2 and the inverses the correction needs travel in the
+ * kernel arguments), reads a and writes k chunks per stripe, pre-zeroes
+ * nothing, uses no global atomics and writes each loc[t] by one plain store
+ * (-ENODEV where the device layer lacks it). */
+int32_t ec_method_decode_checked2(ec_matrix_list_t *list, uint64_t nstripes,
+                                  uintptr_t avail_mask, const void *const *frags, void *out,
+                                  uint32_t *loc, uint64_t *nbad, uint64_t *nmany);
+int32_t ec_method_decode_checked2_device(ec_matrix_list_t *list, int device, void *stream,
+                                         uint64_t nstripes, uintptr_t avail_mask,
+                                         const void *const *frags, void *out, uint32_t *loc);
+
 /* Repairing what locate named: one call that consumes loc[] where it lies and
  * rewrites only the named chunks, closing verify -> locate -> repair.  frags
  * and avail_mask as for ec_method_locate, except that a >= k + 1 bricks are
