@@ -1559,6 +1559,21 @@ int partition(int ndev, uint64_t nstripes, uint64_t align, uint64_t bytes, F fn)
     return 0;
 }
 
+/* The body of an entry point that is one launch on the caller's device and
+ * stream: check the device, select it (DeviceGuard restores the thread's own
+ * on return), drop any stale error so that a failure after it is the
+ * launch's, and run launch(stream). */
+template <typename F>
+int on_device(int device, void *stream, F launch)
+{
+    if (ecd_device_count() <= device || device < 0)
+        return -ENODEV;
+    DeviceGuard dg;
+    clear_stale_error();
+    HIPCHK(hipSetDevice(g_dev_ids[device]));
+    return launch(pick_stream(stream));
+}
+
 } // namespace
 
 extern "C" {
@@ -1600,45 +1615,33 @@ int ecd_has_vander(uint32_t k, uint32_t n)
 int ecd_encode_vander(int device, void *stream, uint32_t k, uint32_t n, uint64_t nstripes,
                       const void *in, void *const *out)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_encode_vander(pick_stream(stream), k, n, nstripes, in, out);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_encode_vander(s, k, n, nstripes, in, out);
+    });
 }
 
 int ecd_combine(int device, void *stream, const ecd_combine_desc_t *d)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_combine(pick_stream(stream), d);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_combine(s, d);
+    });
 }
 
 int ecd_verify(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                const uint8_t *check_brick, uint32_t *bad)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_verify(pick_stream(stream), d, check, check_brick, bad);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_verify(s, d, check, check_brick, bad);
+    });
 }
 
 int ecd_locate(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                uint32_t *loc)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_locate(pick_stream(stream), d, check, check_brick, basis_brick, ratio, loc);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_locate(s, d, check, check_brick, basis_brick, ratio, loc);
+    });
 }
 
 int ecd_decode_checked(int device, void *stream, const ecd_combine_desc_t *d,
@@ -1646,26 +1649,19 @@ int ecd_decode_checked(int device, void *stream, const ecd_combine_desc_t *d,
                        const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *inv,
                        const uint8_t *ginv, void *out, uint32_t *loc)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_decode_checked(pick_stream(stream), d, check, check_brick, basis_brick, ratio, inv,
-                               ginv, out, loc);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_decode_checked(s, d, check, check_brick, basis_brick, ratio, inv, ginv, out,
+                                   loc);
+    });
 }
 
 int ecd_locate2(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_locate2(pick_stream(stream), d, check, check_brick, basis_brick, ratio, ratio1,
-                        pair_inv, loc);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_locate2(s, d, check, check_brick, basis_brick, ratio, ratio1, pair_inv, loc);
+    });
 }
 
 int ecd_decode_checked2(int device, void *stream, const ecd_combine_desc_t *d,
@@ -1674,37 +1670,27 @@ int ecd_decode_checked2(int device, void *stream, const ecd_combine_desc_t *d,
                         const uint8_t *pair_inv, const uint8_t *inv, const uint8_t *ginv,
                         void *out, uint32_t *loc)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_decode_checked2(pick_stream(stream), d, check, check_brick, basis_brick, ratio,
-                                ratio1, pair_inv, inv, ginv, out, loc);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_decode_checked2(s, d, check, check_brick, basis_brick, ratio, ratio1, pair_inv,
+                                    inv, ginv, out, loc);
+    });
 }
 
 int ecd_repair(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
                uint32_t avail, const uint8_t *bset, const uint8_t *coef, const uint32_t *loc)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_repair(pick_stream(stream), k, nstripes, frags, avail, bset, coef, loc);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_repair(s, k, nstripes, frags, avail, bset, coef, loc);
+    });
 }
 
 int ecd_repair2(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
                 uint32_t avail, uint32_t rows, const uint8_t *g, const uint8_t *ginv,
                 const uint8_t *pair_inv, const uint32_t *loc)
 {
-    if (ecd_device_count() <= device || device < 0)
-        return -ENODEV;
-    DeviceGuard dg;
-    clear_stale_error();
-    HIPCHK(hipSetDevice(g_dev_ids[device]));
-    return ecdk_repair2(pick_stream(stream), k, nstripes, frags, avail, rows, g, ginv, pair_inv,
-                        loc);
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_repair2(s, k, nstripes, frags, avail, rows, g, ginv, pair_inv, loc);
+    });
 }
 
 int ecd_sync(int device, void *stream)

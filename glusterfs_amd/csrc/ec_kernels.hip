@@ -14,21 +14,25 @@
  *            8-stripe ec_combine, 16 waves (two blocks fill a CU's 32 wave
  *            slots); both stage by LDS-DMA into a plane-major tile and
  *            multiply by a jump into the searched XOR programs
- *   verify   the consistency check: ec_verify_n, the narrow tile with the
- *            check fragments staged beside the basis, 4 bytes out per stripe
- *   locate   the damaged brick per stripe: ec_locate_n, verify's tile with
- *            the syndromes kept in LDS and a second phase for dirty tiles
- *   locate2  up to two damaged bricks per stripe: ec_locate2_n, locate's two
- *            phases and a third over the candidate pairs for open tiles
+ *   scrub    five kernels on one narrow tile, the check fragments staged
+ *            beside the basis, put together from phases that are each
+ *            written once (ec_kernels_impl.h) and launched by one launcher
+ *            (launch_scrub_tile):
+ *   verify   the consistency check: ec_verify_n, phase 1 (the syndromes),
+ *            4 bytes out per stripe
+ *   locate   the damaged brick per stripe: ec_locate_n, the syndromes kept
+ *            in LDS and phase 2 (the single position) for dirty tiles
+ *   locate2  up to two damaged bricks per stripe: ec_locate2_n, and phase 3
+ *            (the candidate pairs) for open tiles
+ *   checked  a read that checks and corrects: ec_decode_checked_n, phases 1
+ *   decode   and 2, the named basis chunk corrected in LDS, one dense decode
+ *   checked2 the same read around up to two chunks: ec_decode_checked2_n,
+ *   decode   phases 1 to 3, at most four products XORed into the named basis
+ *            chunks in LDS, one dense decode
  *   repair   the chunks locate named: ec_repair_n, a ballot scan of loc[]
  *            and up to four dirty stripes of one brick per wave, no LDS
- *   repair2  the one or two chunks locate2 named: ec_repair2_n, repair's
+ *   repair2  the one or two chunks locate2 named: ec_repair2_n, the same
  *            scan, a pair rebuilt from the syndromes and locate2's tables
- *   checked  a read that checks and corrects: ec_decode_checked_n, locate's
- *   decode   tile, the named basis chunk corrected in LDS, one dense decode
- *   checked2 the same read around up to two chunks: ec_decode_checked2_n,
- *   decode   locate2's three phases, at most four products XORed into the
- *            named basis chunks in LDS, one dense decode
  *   stores   non-temporal on every device-path kernel except the 2+1 / 4+2
  *            register encoders (profiles/kbench_r01_nts.log)
  *   staging  LDS-DMA loads non-temporal for calls whose input exceeds the
@@ -47,6 +51,7 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include <cstddef>
@@ -888,32 +893,50 @@ int ecdk_combine(hipStream_t s, const ecd_combine_desc_t *d)
 
 namespace {
 
-template <int K, int NW, int LA>
-int launch_verify(hipStream_t s, const VerifyArgs &a)
+/* the template arguments of one instantiation of a scrub tile kernel */
+template <int K_, int NW_, int LA_>
+struct ScrubCfg {
+    static constexpr int K = K_, NW = NW_, LA = LA_;
+};
+
+/* The launch of a four-stripe scrub tile kernel, for all five of them.
+ * kernel(ScrubCfg<K, NW, LA>{}) gives the instantiation to run on the packed
+ * arguments a; k, rows and nstripes are the geometry in a, align the OR of
+ * its input addresses, nf the kernel's words per stripe, and a failed launch
+ * is recorded under `what`. */
+template <typename Args, typename Kernel>
+int launch_scrub_tile(hipStream_t s, const Args &a, u32 k, u32 rows, uint64_t nstripes,
+                      uintptr_t align, u32 nf, const char *what, Kernel kernel)
 {
-    const uint64_t g = (a.nstripes + 3) / 4;
+    const uint64_t g = (nstripes + 3) / 4;
     if (g == 0)
         return 0;
     if (g > 0x7fffffffull)
         return -EINVAL;
-    /* at most 31 inputs (ecdk_verify): 62 KiB + 16, under the 64 KiB a launch
-     * takes without raising the kernel's dynamic LDS limit */
-    const size_t lds = verify_n_lds(a.k + a.rows);
-    hipLaunchKernelGGL((ec_verify_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
-    return launch_ok("launch_verify");
-}
-
-/* the k -> K buckets and wave counts of launch_combine_k's narrow tiles;
- * k > 8 runs 8 waves (two 62 KiB tiles of a 16+15 volume share a CU) */
-template <int LA>
-int launch_verify_k(hipStream_t s, const VerifyArgs &a)
-{
-    if (a.k <= 4)
-        return launch_verify<4, 4, LA>(s, a);
-    if (a.k <= 8)
-        return a.nstripes <= (1u << 17) ? launch_verify<8, 8, LA>(s, a)
-                                        : launch_verify<8, 4, LA>(s, a);
-    return launch_verify<16, 8, LA>(s, a);
+    /* at most 31 inputs (the ecdk_ functions check): 62 KiB + 48 with three
+     * words per stripe, under the 64 KiB a launch takes without raising the
+     * kernel's dynamic LDS limit */
+    const size_t lds = scrub_tile_lds(k + rows, nf);
+    auto launch = [&](auto cfg) {
+        const auto fn = kernel(cfg);
+        hipLaunchKernelGGL(fn, dim3((u32)g), dim3(decltype(cfg)::NW * 64), lds, s, a);
+        return launch_ok(what);
+    };
+    /* the k -> K buckets and wave counts of launch_combine_k's narrow tiles;
+     * k > 8 runs 8 waves (two 62 KiB tiles of a 16+15 volume share a CU) */
+    auto bucket = [&](auto la) {
+        constexpr int LA = decltype(la)::value;
+        if (k <= 4)
+            return launch(ScrubCfg<4, 4, LA>{});
+        if (k <= 8)
+            return nstripes <= (1u << 17) ? launch(ScrubCfg<8, 8, LA>{})
+                                          : launch(ScrubCfg<8, 4, LA>{});
+        return launch(ScrubCfg<16, 8, LA>{});
+    };
+    /* the staging policy of ecdk_combine, by the bytes the call reads */
+    const bool nt = nt_staging(nstripes * (k + rows) * ECD_CHUNK) && (align & 15u) == 0;
+    return nt ? bucket(std::integral_constant<int, kLdsDmaNT>{})
+              : bucket(std::integral_constant<int, kLdsDmaDefault>{});
 }
 
 } // namespace
@@ -955,43 +978,13 @@ int ecdk_verify(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
         for (u32 p = 0; p < a.k; ++p)
             a.coef[r * a.kw + (p >> 2)] |= (u32)d->pat[a.k + r * a.k + p] << ((p & 3u) * 8u);
     }
-    /* the staging policy of ecdk_combine, by the bytes the call reads */
-    const bool nt = nt_staging(a.nstripes * (a.k + a.rows) * ECD_CHUNK) && (o & 15u) == 0;
-    return nt ? launch_verify_k<kLdsDmaNT>(s, a) : launch_verify_k<kLdsDmaDefault>(s, a);
+    return launch_scrub_tile(s, a, a.k, a.rows, a.nstripes, o, 1, "launch_verify", [](auto c) {
+        using C = decltype(c);
+        return &ec_verify_n<C::K, C::NW, C::LA>;
+    });
 }
 
 /* ------------------------------------------- locating the damaged brick */
-
-namespace {
-
-template <int K, int NW, int LA>
-int launch_locate(hipStream_t s, const LocateArgs &a)
-{
-    const uint64_t g = (a.nstripes + 3) / 4;
-    if (g == 0)
-        return 0;
-    if (g > 0x7fffffffull)
-        return -EINVAL;
-    /* at most 31 inputs (ecdk_locate): 62 KiB + 32, under the 64 KiB a launch
-     * takes without raising the kernel's dynamic LDS limit */
-    const size_t lds = locate_n_lds(a.k + a.rows);
-    hipLaunchKernelGGL((ec_locate_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
-    return launch_ok("launch_locate");
-}
-
-/* the buckets and wave counts of launch_verify_k */
-template <int LA>
-int launch_locate_k(hipStream_t s, const LocateArgs &a)
-{
-    if (a.k <= 4)
-        return launch_locate<4, 4, LA>(s, a);
-    if (a.k <= 8)
-        return a.nstripes <= (1u << 17) ? launch_locate<8, 8, LA>(s, a)
-                                        : launch_locate<8, 4, LA>(s, a);
-    return launch_locate<16, 8, LA>(s, a);
-}
-
-} // namespace
 
 /* The arguments of ec_locate_n from what ecdk_locate is given; *align gets
  * the OR of the input addresses (the staging policy wants it). */
@@ -1049,42 +1042,13 @@ int ecdk_locate(hipStream_t s, const ecd_combine_desc_t *d, const void *const *c
     uintptr_t o = 0;
     if (int rc = pack_locate(d, check, check_brick, basis_brick, ratio, loc, a, &o))
         return rc;
-    /* the staging policy of ecdk_verify, by the bytes the call reads */
-    const bool nt = nt_staging(a.nstripes * (a.k + a.rows) * ECD_CHUNK) && (o & 15u) == 0;
-    return nt ? launch_locate_k<kLdsDmaNT>(s, a) : launch_locate_k<kLdsDmaDefault>(s, a);
+    return launch_scrub_tile(s, a, a.k, a.rows, a.nstripes, o, 2, "launch_locate", [](auto c) {
+        using C = decltype(c);
+        return &ec_locate_n<C::K, C::NW, C::LA>;
+    });
 }
 
 /* ------------------------------------------- a read that checks and corrects */
-
-namespace {
-
-template <int K, int NW, int LA>
-int launch_decode_checked(hipStream_t s, const DecodeCheckedArgs &a)
-{
-    const uint64_t g = (a.l.nstripes + 3) / 4;
-    if (g == 0)
-        return 0;
-    if (g > 0x7fffffffull)
-        return -EINVAL;
-    /* the tile and the words of ec_locate_n: at most 62 KiB + 32 */
-    const size_t lds = locate_n_lds(a.l.k + a.l.rows);
-    hipLaunchKernelGGL((ec_decode_checked_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
-    return launch_ok("launch_decode_checked");
-}
-
-/* the buckets and wave counts of launch_locate_k */
-template <int LA>
-int launch_decode_checked_k(hipStream_t s, const DecodeCheckedArgs &a)
-{
-    if (a.l.k <= 4)
-        return launch_decode_checked<4, 4, LA>(s, a);
-    if (a.l.k <= 8)
-        return a.l.nstripes <= (1u << 17) ? launch_decode_checked<8, 8, LA>(s, a)
-                                          : launch_decode_checked<8, 4, LA>(s, a);
-    return launch_decode_checked<16, 8, LA>(s, a);
-}
-
-} // namespace
 
 /* As ecdk_locate, then inv: k x k bytes, the decode matrix of the basis (row
  * j gives output chunk j); ginv: k bytes, 1 / coefficient of row 0; out:
@@ -1113,44 +1077,14 @@ int ecdk_decode_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *
         for (u32 j = 0; j < k; ++j)
             a.inv[j * kw + (p >> 2)] |= (u32)inv[j * k + p] << ((p & 3u) * 8u);
     }
-    /* the staging policy of ecdk_locate, by the bytes the call reads */
-    const bool nt = nt_staging(a.l.nstripes * (k + a.l.rows) * ECD_CHUNK) && (o & 15u) == 0;
-    return nt ? launch_decode_checked_k<kLdsDmaNT>(s, a)
-              : launch_decode_checked_k<kLdsDmaDefault>(s, a);
+    return launch_scrub_tile(s, a, k, a.l.rows, a.l.nstripes, o, 2, "launch_decode_checked",
+                             [](auto c) {
+        using C = decltype(c);
+        return &ec_decode_checked_n<C::K, C::NW, C::LA>;
+    });
 }
 
 /* ------------------------------------------ locating up to two bricks */
-
-namespace {
-
-template <int K, int NW, int LA>
-int launch_locate2(hipStream_t s, const Locate2Args &a)
-{
-    const uint64_t g = (a.l.nstripes + 3) / 4;
-    if (g == 0)
-        return 0;
-    if (g > 0x7fffffffull)
-        return -EINVAL;
-    /* at most 31 inputs (ecdk_locate2): 62 KiB + 48, under the 64 KiB a launch
-     * takes without raising the kernel's dynamic LDS limit */
-    const size_t lds = locate2_n_lds(a.l.k + a.l.rows);
-    hipLaunchKernelGGL((ec_locate2_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
-    return launch_ok("launch_locate2");
-}
-
-/* the buckets and wave counts of launch_locate_k */
-template <int LA>
-int launch_locate2_k(hipStream_t s, const Locate2Args &a)
-{
-    if (a.l.k <= 4)
-        return launch_locate2<4, 4, LA>(s, a);
-    if (a.l.k <= 8)
-        return a.l.nstripes <= (1u << 17) ? launch_locate2<8, 8, LA>(s, a)
-                                          : launch_locate2<8, 4, LA>(s, a);
-    return launch_locate2<16, 8, LA>(s, a);
-}
-
-} // namespace
 
 /* The arguments of ec_locate2_n from what ecdk_locate2 is given: pack_locate,
  * then ratio1, the pairs' inverses and their positions. */
@@ -1193,42 +1127,14 @@ int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *
     if (int rc = pack_locate2(d, check, check_brick, basis_brick, ratio, ratio1, pair_inv, loc, a,
                               &o))
         return rc;
-    /* the staging policy of ecdk_locate, by the bytes the call reads */
-    const bool nt = nt_staging(a.l.nstripes * (a.l.k + a.l.rows) * ECD_CHUNK) && (o & 15u) == 0;
-    return nt ? launch_locate2_k<kLdsDmaNT>(s, a) : launch_locate2_k<kLdsDmaDefault>(s, a);
+    return launch_scrub_tile(s, a, a.l.k, a.l.rows, a.l.nstripes, o, 3, "launch_locate2",
+                             [](auto c) {
+        using C = decltype(c);
+        return &ec_locate2_n<C::K, C::NW, C::LA>;
+    });
 }
 
 /* ------------------------------------- a read that corrects up to two chunks */
-
-namespace {
-
-template <int K, int NW, int LA>
-int launch_decode_checked2(hipStream_t s, const DecodeChecked2Args &a)
-{
-    const uint64_t g = (a.l2.l.nstripes + 3) / 4;
-    if (g == 0)
-        return 0;
-    if (g > 0x7fffffffull)
-        return -EINVAL;
-    /* the tile and the words of ec_locate2_n: at most 62 KiB + 48 */
-    const size_t lds = locate2_n_lds(a.l2.l.k + a.l2.l.rows);
-    hipLaunchKernelGGL((ec_decode_checked2_n<K, NW, LA>), dim3((u32)g), dim3(NW * 64), lds, s, a);
-    return launch_ok("launch_decode_checked2");
-}
-
-/* the buckets and wave counts of launch_locate2_k */
-template <int LA>
-int launch_decode_checked2_k(hipStream_t s, const DecodeChecked2Args &a)
-{
-    if (a.l2.l.k <= 4)
-        return launch_decode_checked2<4, 4, LA>(s, a);
-    if (a.l2.l.k <= 8)
-        return a.l2.l.nstripes <= (1u << 17) ? launch_decode_checked2<8, 8, LA>(s, a)
-                                             : launch_decode_checked2<8, 4, LA>(s, a);
-    return launch_decode_checked2<16, 8, LA>(s, a);
-}
-
-} // namespace
 
 /* As ecdk_locate2, then inv: k x k bytes, the decode matrix of the basis (row
  * j gives output chunk j); ginv: 2 x k bytes, 1 / coefficient of row 0, then
@@ -1259,10 +1165,11 @@ int ecdk_decode_checked2(hipStream_t s, const ecd_combine_desc_t *d, const void 
         for (u32 j = 0; j < k; ++j)
             a.inv[j * kw + (p >> 2)] |= (u32)inv[j * k + p] << ((p & 3u) * 8u);
     }
-    /* the staging policy of ecdk_locate2, by the bytes the call reads */
-    const bool nt = nt_staging(a.l2.l.nstripes * (k + a.l2.l.rows) * ECD_CHUNK) && (o & 15u) == 0;
-    return nt ? launch_decode_checked2_k<kLdsDmaNT>(s, a)
-              : launch_decode_checked2_k<kLdsDmaDefault>(s, a);
+    return launch_scrub_tile(s, a, k, a.l2.l.rows, a.l2.l.nstripes, o, 3, "launch_decode_checked2",
+                             [](auto c) {
+        using C = decltype(c);
+        return &ec_decode_checked2_n<C::K, C::NW, C::LA>;
+    });
 }
 
 /* ------------------------------------------- repairing the named chunks */

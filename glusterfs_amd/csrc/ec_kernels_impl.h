@@ -1488,86 +1488,6 @@ struct VerifyArgs {
     u32 coef[kMaxPatWords];
 };
 
-/* ec_method_verify_device: do the stored fragments of `rows` bricks agree
- * with what the k basis fragments imply?  The narrow combine's shape (T = 4
- * stripes per block, 16 lanes per chunk, one dword column of all 8 planes
- * per lane) with the check fragments staged beside the basis: the tile is
- * (k + rows) * 2 KiB, then one u32 flag per stripe.  A wave item is one row
- * for the 4 stripes: predict the row's chunk (the heal product), XOR the
- * stored chunk's planes in from LDS, OR the 8 words; the 16 lanes of a
- * stripe vote by ballot and one of them ORs the row's brick bit into the
- * stripe's flag in LDS.  Each flag leaves by one plain dword store, so
- * nothing is pre-zeroed and there are no global atomics; stripes past
- * nstripes are neither staged nor stored. */
-template <int K, int NW, int LA = kLdsDmaDefault>
-__global__ __launch_bounds__(NW * 64) void ec_verify_n(const VerifyArgs a)
-{
-    constexpr u32 T = 4;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const u32 tid = threadIdx.x;
-    const u32 k = a.k, ni = a.k + a.rows;
-    const uint64_t t0 = (uint64_t)blockIdx.x * T;
-    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 lane = tid & 63u;
-    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
-    if (tid < T)
-        flags[tid] = 0;
-    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
-        return a.in[p] + st * ECD_CHUNK;
-    }, ni, t0, a.nstripes, wave, lane);
-    __syncthreads();
-    const u32 cs = lane >> 4, cc = lane & 15u;
-    const uint8_t *col = lds + cs * 64u + cc * 4u;
-    const bool live = t0 + cs < a.nstripes;
-    for (u32 r = wave; r < a.rows; r += NW) {
-        const u32 rw = a.kw * r;
-        const u32 w0 = a.coef[rw];
-        const u32 w1 = K > 4 ? a.coef[rw + 1] : 0u;
-        const u32 w2 = K > 8 ? a.coef[rw + 2] : 0u;
-        const u32 w3 = K > 12 ? a.coef[rw + 3] : 0u;
-        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
-        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
-        u32 acc[8][1], y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            acc[b][0] = 0;
-#pragma unroll 1
-        for (u32 p = 0; p < k; ++p) {
-            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
-            cl = (cl >> 8) | (ch << 56);
-            ch >>= 8;
-            if (c == 0)
-                continue;
-            const uint8_t *src = col + p * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-            ecgf::mul_xor_jt<1>(c, acc, y);
-        }
-        /* prediction ^ stored chunk: any bit left is a mismatch */
-        const uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
-        u32 d = 0;
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(chk + (u32)b * (T * 64u));
-        const uint64_t vote = __ballot(live && d != 0);
-        const u32 brick = __builtin_amdgcn_readfirstlane((a.brick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
-        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
-            atomicOr(&flags[cs], 1u << brick);
-    }
-    __syncthreads();
-    if (tid < T && t0 + tid < a.nstripes)
-        a.bad[t0 + tid] = flags[tid];
-}
-
-/* dynamic LDS of an ec_verify_n launch: the tile and the 4 stripe flags */
-constexpr size_t verify_n_lds(u32 inputs)
-{
-    return (size_t)inputs * 4 * ECD_CHUNK + 4 * sizeof(u32);
-}
-
-/* ------------------------------------------- locating the damaged brick */
-
 constexpr u32 kLocateMany = 0x80000000u;      /* EC_MI355X_LOCATE_MANY */
 constexpr u32 kLocateWords = ECD_MAX_K / 4 * (ECD_MAX_ROWS / 2); /* 16 rows of 4 words */
 
@@ -1586,139 +1506,6 @@ struct LocateArgs {
     u32 ratio[kLocateWords];
 };
 
-/* ec_method_locate_device: which brick's chunk is wrong?  Phase 1 is
- * ec_verify_n (the same tile, staging and row spread) except that the lane
- * keeps the syndrome -- prediction ^ stored, 8 words -- in the check chunk's
- * own LDS slot (it owns that dword column and no other row reads the slot),
- * and the stripe's flag collects the brick bits of its non-zero rows.  A tile
- * whose four flags are zero stores four zeros and is done: the normal case,
- * at verify's cost plus the write-back.  The decision is read from LDS after
- * a barrier, so the whole block takes it together.
- *
- * Phase 2, for a tile with a dirty stripe.  A flag of one bit is that check
- * brick.  With two or more, an error e in basis input p alone would give
- * s_r = G[r][p] * e for every row, i.e. s_r = q[r][p] * s_0: the basis
- * positions are spread over the waves, each tests that equality for rows
- * 1 .. rows-1 over its dword column, the 16 lanes of a stripe vote, and a
- * position that passes ORs its brick bit into the stripe's result word (at
- * most one can pass: two would make the stripe consistent).  No barrier sits
- * in a loop, so waves without a row or a position reach every one.  Each
- * loc[t] leaves by one plain dword store. */
-template <int K, int NW, int LA = kLdsDmaDefault>
-__global__ __launch_bounds__(NW * 64) void ec_locate_n(const LocateArgs a)
-{
-    constexpr u32 T = 4;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const u32 tid = threadIdx.x;
-    const u32 k = a.k, ni = a.k + a.rows;
-    const uint64_t t0 = (uint64_t)blockIdx.x * T;
-    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 lane = tid & 63u;
-    /* flags[s]: brick bits of stripe s's non-zero rows; flags[T + s]: the
-     * brick bit of the basis position that explains them */
-    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
-    if (tid < 2 * T)
-        flags[tid] = 0;
-    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
-        return a.in[p] + st * ECD_CHUNK;
-    }, ni, t0, a.nstripes, wave, lane);
-    __syncthreads();
-    const u32 cs = lane >> 4, cc = lane & 15u;
-    uint8_t *col = lds + cs * 64u + cc * 4u;
-    const bool live = t0 + cs < a.nstripes;
-    for (u32 r = wave; r < a.rows; r += NW) {
-        const u32 rw = a.kw * r;
-        const u32 w0 = a.coef[rw];
-        const u32 w1 = K > 4 ? a.coef[rw + 1] : 0u;
-        const u32 w2 = K > 8 ? a.coef[rw + 2] : 0u;
-        const u32 w3 = K > 12 ? a.coef[rw + 3] : 0u;
-        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
-        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
-        u32 acc[8][1], y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            acc[b][0] = 0;
-#pragma unroll 1
-        for (u32 p = 0; p < k; ++p) {
-            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
-            cl = (cl >> 8) | (ch << 56);
-            ch >>= 8;
-            if (c == 0)
-                continue;
-            const uint8_t *src = col + p * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-            ecgf::mul_xor_jt<1>(c, acc, y);
-        }
-        /* the syndrome replaces the stored chunk in LDS */
-        uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
-        u32 d = 0;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (T * 64u));
-            const u32 s = acc[b][0] ^ *w;
-            *w = s;
-            d |= s;
-        }
-        const uint64_t vote = __ballot(live && d != 0);
-        const u32 brick = __builtin_amdgcn_readfirstlane((a.cbrick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
-        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
-            atomicOr(&flags[cs], 1u << brick);
-    }
-    __syncthreads();
-    const u32 any = __builtin_amdgcn_readfirstlane(flags[0] | flags[1] | flags[2] | flags[3]);
-    if (any == 0) {
-        if (tid < T && t0 + tid < a.nstripes)
-            a.loc[t0 + tid] = 0;
-        return;
-    }
-    /* a stripe with two or more non-zero rows looks for its basis position
-     * (stripes past nstripes have no flag) */
-    const u32 mine = flags[cs];
-    const bool open = (mine & (mine - 1u)) != 0;
-    const uint8_t *s0 = col + k * (T * ECD_CHUNK);
-    for (u32 p = wave; p < k; p += NW) {
-        u32 y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            y[b][0] = *reinterpret_cast<const u32 *>(s0 + (u32)b * (T * 64u));
-        u32 d = 0;
-#pragma unroll 1
-        for (u32 r = 1; r < a.rows; ++r) {
-            const u32 q = __builtin_amdgcn_readfirstlane(
-                (a.ratio[(r - 1) * a.kw + (p >> 2)] >> ((p & 3u) * 8u)) & 0xFFu);
-            u32 acc[8][1];
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                acc[b][0] = 0;
-            if (q != 0)
-                ecgf::mul_xor_jt<1>(q, acc, y);
-            const uint8_t *sr = col + (k + r) * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
-        }
-        const uint64_t vote = __ballot(d != 0);
-        const u32 brick = __builtin_amdgcn_readfirstlane((a.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
-        if (cc == 0 && open && ((vote >> (cs * 16u)) & 0xFFFFu) == 0)
-            atomicOr(&flags[T + cs], 1u << brick);
-    }
-    __syncthreads();
-    if (tid < T && t0 + tid < a.nstripes) {
-        const u32 f = flags[tid], b = flags[T + tid];
-        a.loc[t0 + tid] = (f & (f - 1u)) == 0 ? f : b ? b : kLocateMany;
-    }
-}
-
-/* dynamic LDS of an ec_locate_n launch: the tile and two words per stripe */
-constexpr size_t locate_n_lds(u32 inputs)
-{
-    return (size_t)inputs * 4 * ECD_CHUNK + 8 * sizeof(u32);
-}
-
-/* ------------------------------------------- a read that checks and corrects */
-
 /* Kernel arguments of ec_decode_checked_n: LocateArgs, then the decoded
  * output (stripe t at out + t * k * 512, any byte alignment), B as a brick
  * mask, inv(B) laid out like the coefficients (row j at word j * kw) and the
@@ -1730,190 +1517,6 @@ struct DecodeCheckedArgs {
     u32 inv[ECD_MAX_K * (ECD_MAX_K / 4)];
     u32 ginv[ECD_MAX_K / 4];
 };
-
-/* ec_method_decode_checked_device: decode the k lowest bricks and, in the
- * same pass, check them against the others and correct a single bad chunk.
- * Phases 1 and 2 are ec_locate_n's, statement for statement: the tile, the
- * syndromes left in the check chunks' LDS slots, the flags and the result
- * words.  A clean tile skips phase 2 and the correction.
- *
- * The correction, for a stripe whose result word names basis position p: the
- * error in p is e = s_0 / G[0][p] (s_0 = G[0][p] * e when p alone is wrong),
- * and XORing e into p's LDS slot puts the basis chunks on the one codeword
- * the other a - 1 chunks lie on, so that one dense decode with inv(B) gives
- * what inv(B_i) would give from the undamaged chunks.  The jump-table
- * multiply wants a wave-uniform coefficient and p differs per stripe: the
- * tile's four stripes go one per wave item, each on its own 16 lanes, around
- * one multiply site.  MANY stripes, check-brick stripes and stripes past
- * nstripes are left alone.
- *
- * The decode: the k output rows are spread over the waves like the check rows
- * of phase 1; row j is the sum of inv(B)[j][p] * x_p over the basis slots and
- * leaves by dword stores, 64 contiguous bytes per plane and stripe.  No
- * barrier sits in a loop, and every decision around one is read from LDS
- * after a barrier, so the whole block takes it together. */
-template <int K, int NW, int LA = kLdsDmaDefault>
-__global__ __launch_bounds__(NW * 64) void ec_decode_checked_n(const DecodeCheckedArgs a)
-{
-    constexpr u32 T = 4;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const u32 tid = threadIdx.x;
-    const u32 k = a.l.k, ni = a.l.k + a.l.rows;
-    const uint64_t t0 = (uint64_t)blockIdx.x * T;
-    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 lane = tid & 63u;
-    /* flags[s], flags[T + s]: as in ec_locate_n */
-    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
-    if (tid < 2 * T)
-        flags[tid] = 0;
-    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
-        return a.l.in[p] + st * ECD_CHUNK;
-    }, ni, t0, a.l.nstripes, wave, lane);
-    __syncthreads();
-    const u32 cs = lane >> 4, cc = lane & 15u;
-    uint8_t *col = lds + cs * 64u + cc * 4u;
-    const bool live = t0 + cs < a.l.nstripes;
-    for (u32 r = wave; r < a.l.rows; r += NW) {
-        const u32 rw = a.l.kw * r;
-        const u32 w0 = a.l.coef[rw];
-        const u32 w1 = K > 4 ? a.l.coef[rw + 1] : 0u;
-        const u32 w2 = K > 8 ? a.l.coef[rw + 2] : 0u;
-        const u32 w3 = K > 12 ? a.l.coef[rw + 3] : 0u;
-        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
-        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
-        u32 acc[8][1], y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            acc[b][0] = 0;
-#pragma unroll 1
-        for (u32 p = 0; p < k; ++p) {
-            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
-            cl = (cl >> 8) | (ch << 56);
-            ch >>= 8;
-            if (c == 0)
-                continue;
-            const uint8_t *src = col + p * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-            ecgf::mul_xor_jt<1>(c, acc, y);
-        }
-        /* the syndrome replaces the stored chunk in LDS */
-        uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
-        u32 d = 0;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (T * 64u));
-            const u32 s = acc[b][0] ^ *w;
-            *w = s;
-            d |= s;
-        }
-        const uint64_t vote = __ballot(live && d != 0);
-        const u32 brick = __builtin_amdgcn_readfirstlane((a.l.cbrick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
-        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
-            atomicOr(&flags[cs], 1u << brick);
-    }
-    __syncthreads();
-    const u32 any = __builtin_amdgcn_readfirstlane(flags[0] | flags[1] | flags[2] | flags[3]);
-    if (any != 0) {
-        /* a stripe with two or more non-zero rows looks for its basis position
-         * (stripes past nstripes have no flag) */
-        const u32 mine = flags[cs];
-        const bool open = (mine & (mine - 1u)) != 0;
-        const uint8_t *s0 = col + k * (T * ECD_CHUNK);
-        for (u32 p = wave; p < k; p += NW) {
-            u32 y[8][1];
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(s0 + (u32)b * (T * 64u));
-            u32 d = 0;
-#pragma unroll 1
-            for (u32 r = 1; r < a.l.rows; ++r) {
-                const u32 q = __builtin_amdgcn_readfirstlane(
-                    (a.l.ratio[(r - 1) * a.l.kw + (p >> 2)] >> ((p & 3u) * 8u)) & 0xFFu);
-                u32 acc[8][1];
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    acc[b][0] = 0;
-                if (q != 0)
-                    ecgf::mul_xor_jt<1>(q, acc, y);
-                const uint8_t *sr = col + (k + r) * (T * ECD_CHUNK);
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
-            }
-            const uint64_t vote = __ballot(d != 0);
-            const u32 brick = __builtin_amdgcn_readfirstlane((a.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
-            if (cc == 0 && open && ((vote >> (cs * 16u)) & 0xFFFFu) == 0)
-                atomicOr(&flags[T + cs], 1u << brick);
-        }
-        __syncthreads();
-        /* stripe s of the tile, on lanes 16 s .. 16 s + 15 of one wave: its
-         * words are final, and a named basis brick is the one bit of the
-         * second while the first has two or more (0 for stripes past
-         * nstripes).  c = 0 (nothing to correct) multiplies to zero. */
-        for (u32 s = wave; s < T; s += NW) {
-            const u32 f = __builtin_amdgcn_readfirstlane(flags[s]);
-            const u32 bb = __builtin_amdgcn_readfirstlane(flags[T + s]);
-            const bool fix = (f & (f - 1u)) != 0 && bb != 0;
-            const u32 p = fix ? (u32)__builtin_popcount(a.bmask & (bb - 1u)) : 0u;
-            const u32 c = __builtin_amdgcn_readfirstlane(
-                fix ? (a.ginv[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu : 0u);
-            if (c == 0)
-                continue;
-            u32 acc[8][1], y[8][1];
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                acc[b][0] = 0;
-                y[b][0] = *reinterpret_cast<const u32 *>(s0 + (u32)b * (T * 64u));
-            }
-            ecgf::mul_xor_jt<1>(c, acc, y);
-            if (cs == s) {
-                uint8_t *x = col + p * (T * ECD_CHUNK);
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    *reinterpret_cast<u32 *>(x + (u32)b * (T * 64u)) ^= acc[b][0];
-            }
-        }
-        __syncthreads();
-    }
-    /* the decode of the (corrected) basis chunks */
-    uint8_t *o = a.out + (t0 + cs) * ((uint64_t)k * ECD_CHUNK) + cc * 4u;
-    for (u32 j = wave; j < k; j += NW) {
-        const u32 rw = a.l.kw * j;
-        const u32 w0 = a.inv[rw];
-        const u32 w1 = K > 4 ? a.inv[rw + 1] : 0u;
-        const u32 w2 = K > 8 ? a.inv[rw + 2] : 0u;
-        const u32 w3 = K > 12 ? a.inv[rw + 3] : 0u;
-        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
-        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
-        u32 acc[8][1], y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            acc[b][0] = 0;
-#pragma unroll 1
-        for (u32 p = 0; p < k; ++p) {
-            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
-            cl = (cl >> 8) | (ch << 56);
-            ch >>= 8;
-            if (c == 0)
-                continue;
-            const uint8_t *src = col + p * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-            ecgf::mul_xor_jt<1>(c, acc, y);
-        }
-        if (live)
-            store_chunk<1, true>(o + j * ECD_CHUNK, acc);
-    }
-    if (tid < T && t0 + tid < a.l.nstripes) {
-        const u32 f = flags[tid], b = flags[T + tid];
-        a.l.loc[t0 + tid] = (f & (f - 1u)) == 0 ? f : b ? b : kLocateMany;
-    }
-}
-
-/* ------------------------------------------ locating up to two bricks */
 
 constexpr u32 kLocate2Pairs = ECD_MAX_K * (ECD_MAX_K - 1) / 2;   /* C(16, 2) */
 
@@ -1933,17 +1536,286 @@ struct Locate2Args {
     u32 npairs, pad;
 };
 
-/* ec_method_locate2_device: which one or two bricks' chunks are wrong?
- * Phases 1 and 2 are ec_locate_n's, statement for statement: the tile, the
- * syndromes kept in the check chunks' LDS slots, the block-uniform early exit
- * of a clean tile, the basis position that alone explains a stripe.  A third
- * word per stripe, flags[2T + s], collects the brick bits of a pair.
- *
- * After phase 2 a stripe is still open when three or more syndromes are
- * non-zero and no basis position passed (exactly two non-zero syndromes are
- * those two check bricks: nothing to compute).  A tile without an open
- * stripe stores its four words and is done; that too is read from LDS after
- * a barrier.  Phase 3 spreads 2k + C(k, 2) candidates over the waves:
+/* Kernel arguments of ec_decode_checked2_n: Locate2Args, then the decoded
+ * output (stripe t at out + t * k * 512, any byte alignment), B as a brick
+ * mask, inv(B) laid out like the coefficients (row j at word j * kw) and the
+ * k bytes 1 / G[0][p] (ginv[0 ..]) and 1 / G[1][p] (ginv[ECD_MAX_K / 4 ..]).
+ * 2,016 bytes in all. */
+struct DecodeChecked2Args {
+    Locate2Args l2;
+    uint8_t *out;
+    u32 bmask, pad;
+    u32 inv[ECD_MAX_K * (ECD_MAX_K / 4)];
+    u32 ginv[2 * (ECD_MAX_K / 4)];
+};
+
+/* ------------------------------------------ scrub: the phases, once each */
+
+/* The five tile kernels below share the narrow combine's shape: T = 4 stripes
+ * per block, 16 lanes per chunk, one dword column of all 8 planes per lane,
+ * with the check fragments staged beside the basis.  The tile is (k + rows) *
+ * 2 KiB, input p's slot at p * 2 KiB and plane-major as stage_tile lays it,
+ * then up to three u32 words per stripe:
+ *   flags[s]       the brick bits of stripe s's non-zero rows (phase 1)
+ *   flags[T + s]   the brick bit of the basis position that explains them
+ *                  (phase 2)
+ *   flags[2T + s]  the brick bits of the pair that does (phase 3)
+ * Each phase is written once, here; a kernel is a sequence of phases with its
+ * barriers and early exits in its own body.  What every phase keeps to:
+ *  - no barrier sits in a loop or in a phase, so waves without a row, a
+ *    position or a candidate reach every one;
+ *  - every decision around a barrier is read from LDS after a barrier, so the
+ *    whole block takes it together;
+ *  - the jump-table multiply wants a wave-uniform coefficient, so every choice
+ *    around it is wave-uniform, and a phase has one multiply site (about
+ *    26 KiB of code each) in a loop that is not unrolled;
+ *  - each result word leaves by one plain dword store, so nothing is
+ *    pre-zeroed and there are no global atomics; stripes past nstripes are
+ *    neither staged nor stored. */
+constexpr u32 kScrubT = 4;
+constexpr u32 kScrubSlot = kScrubT * ECD_CHUNK;     /* one input's part of the tile */
+
+/* byte i of a table packed four bytes to a word, lowest first */
+__device__ __forceinline__ u32 packed_byte(const u32 *tab, u32 i)
+{
+    return (tab[i >> 2] >> ((i & 3u) * 8u)) & 0xFFu;
+}
+
+/* the lane's dword column of one tile slot: a word of each of the 8 planes */
+__device__ __forceinline__ void read_column(const uint8_t *slot, u32 (&y)[8][1])
+{
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+        y[b][0] = *reinterpret_cast<const u32 *>(slot + (u32)b * (kScrubT * 64u));
+}
+
+/* d with every bit in which acc differs from the lane's column of a slot */
+__device__ __forceinline__ u32 or_diff(u32 d, const uint8_t *slot, const u32 (&acc)[8][1])
+{
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+        d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(slot + (u32)b * (kScrubT * 64u));
+    return d;
+}
+
+__device__ __forceinline__ void xor_column(uint8_t *slot, const u32 (&acc)[8][1])
+{
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+        *reinterpret_cast<u32 *>(slot + (u32)b * (kScrubT * 64u)) ^= acc[b][0];
+}
+
+/* Where a thread stands in its block's tile: stripe t0 + cs on lanes 16 cs ..
+ * 16 cs + 15 of every wave, dword column cc; col is that column in slot 0. */
+struct ScrubTile {
+    uint64_t t0;
+    u32 tid, wave, lane;    /* wave: wave-uniform */
+    u32 cs, cc;
+    bool live;          /* stripe t0 + cs exists */
+    uint8_t *col;
+    u32 *flags;
+};
+
+/* Clear the NF words per stripe and stage in[0 .. ni), the basis and then the
+ * check chunks, by LDS-DMA.  The caller's barrier ends it, and scrub_place
+ * after that barrier fills in the thread's column. */
+template <u32 NF, int NW, int LA, typename A>
+__device__ __forceinline__ ScrubTile scrub_stage(uint8_t *lds, const A &a)
+{
+    ScrubTile t;
+    const u32 ni = a.k + a.rows;
+    t.tid = threadIdx.x;
+    t.t0 = (uint64_t)blockIdx.x * kScrubT;
+    t.wave = __builtin_amdgcn_readfirstlane(t.tid >> 6);
+    t.lane = t.tid & 63u;
+    t.flags = reinterpret_cast<u32 *>(lds + ni * kScrubSlot);
+    if (t.tid < NF * kScrubT)
+        t.flags[t.tid] = 0;
+    stage_tile<kScrubT, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        return a.in[p] + st * ECD_CHUNK;
+    }, ni, t.t0, a.nstripes, t.wave, t.lane);
+    return t;
+}
+
+__device__ __forceinline__ void scrub_place(ScrubTile &t, uint8_t *lds, uint64_t nstripes)
+{
+    t.cs = t.lane >> 4;
+    t.cc = t.lane & 15u;
+    t.col = lds + t.cs * 64u + t.cc * 4u;
+    t.live = t.t0 + t.cs < nstripes;
+}
+
+/* dynamic LDS of a scrub tile launch: the tile and nf words for each of its
+ * 4 stripes */
+constexpr size_t scrub_tile_lds(u32 inputs, u32 nf)
+{
+    return (size_t)inputs * kScrubSlot + nf * kScrubT * sizeof(u32);
+}
+
+/* Row `row` of a coefficient table (kw words a row, a byte per input) times
+ * the tile's k basis slots, for the lane's column.  The row's coefficients
+ * are a 128-bit scalar shift register, as in ec_combine_n; K bounds the words
+ * loaded.  The loop is not unrolled: every copy of its body is a copy of the
+ * multiply site. */
+template <int K>
+__device__ __forceinline__ void row_product(const u32 *words, u32 row, u32 kw, u32 k,
+                                            const uint8_t *col, u32 (&acc)[8][1])
+{
+    const u32 rw = kw * row;
+    const u32 w0 = words[rw];
+    const u32 w1 = K > 4 ? words[rw + 1] : 0u;
+    const u32 w2 = K > 8 ? words[rw + 2] : 0u;
+    const u32 w3 = K > 12 ? words[rw + 3] : 0u;
+    uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
+    uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
+    u32 y[8][1];
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+        acc[b][0] = 0;
+#pragma unroll 1
+    for (u32 p = 0; p < k; ++p) {
+        const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
+        cl = (cl >> 8) | (ch << 56);
+        ch >>= 8;
+        if (c == 0)
+            continue;
+        read_column(col + p * kScrubSlot, y);
+        ecgf::mul_xor_jt<1>(c, acc, y);
+    }
+}
+
+/* Phase 1, the syndromes.  A wave item is one check row for the tile's 4
+ * stripes: predict the row's chunk from the basis (the heal product), XOR the
+ * stored chunk's planes in from LDS -- any bit left is a mismatch -- and OR
+ * the 8 words; the 16 lanes of a stripe vote by ballot and one of them ORs
+ * the row's brick bit (a byte of `brick` per row) into flags[s].  With KEEP
+ * the syndrome, prediction ^ stored, replaces the stored chunk in its LDS
+ * slot for the later phases: the lane owns that dword column and no other row
+ * reads the slot. */
+template <int K, int NW, bool KEEP>
+__device__ __forceinline__ void scrub_syndromes(const ScrubTile &t, const u32 *coef,
+                                                const u32 *brick, u32 k, u32 kw, u32 rows)
+{
+    for (u32 r = t.wave; r < rows; r += NW) {
+        u32 acc[8][1];
+        row_product<K>(coef, r, kw, k, t.col, acc);
+        uint8_t *chk = t.col + (k + r) * kScrubSlot;
+        u32 d = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (kScrubT * 64u));
+            const u32 s = acc[b][0] ^ *w;
+            if constexpr (KEEP)
+                *w = s;
+            d |= s;
+        }
+        const uint64_t vote = __ballot(t.live && d != 0);
+        const u32 bit = __builtin_amdgcn_readfirstlane(packed_byte(brick, r));
+        if (t.cc == 0 && ((vote >> (t.cs * 16u)) & 0xFFFFu) != 0)
+            atomicOr(&t.flags[t.cs], 1u << bit);
+    }
+}
+
+/* block-uniform, from LDS after phase 1's barrier: is any stripe of the tile
+ * dirty?  A clean tile, the normal case, needs no later phase. */
+__device__ __forceinline__ bool scrub_dirty(const ScrubTile &t)
+{
+    return __builtin_amdgcn_readfirstlane(t.flags[0] | t.flags[1] | t.flags[2] | t.flags[3]) != 0;
+}
+
+/* Phase 2, for a tile with a dirty stripe: the basis position that alone
+ * explains a stripe.  A flag of one bit is that check brick.  With two or
+ * more, an error e in basis input p alone would give s_r = G[r][p] * e for
+ * every row, i.e. s_r = q[r][p] * s_0: the basis positions are spread over
+ * the waves, each tests that equality for rows 1 .. rows-1 over its dword
+ * column, the 16 lanes of a stripe vote, and a position that passes ORs its
+ * brick bit into flags[T + s].  At most one can pass (two would make the
+ * stripe consistent), so no order is needed.  Stripes past nstripes have no
+ * flag and stay closed. */
+template <int NW>
+__device__ __forceinline__ void scrub_single(const ScrubTile &t, const LocateArgs &a)
+{
+    const u32 mine = t.flags[t.cs];
+    const bool open = (mine & (mine - 1u)) != 0;
+    const uint8_t *syn = t.col + a.k * kScrubSlot;
+    for (u32 p = t.wave; p < a.k; p += NW) {
+        u32 y[8][1];
+        read_column(syn, y);
+        u32 d = 0;
+#pragma unroll 1
+        for (u32 r = 1; r < a.rows; ++r) {
+            const u32 q = __builtin_amdgcn_readfirstlane(packed_byte(a.ratio + (r - 1) * a.kw, p));
+            u32 acc[8][1] = {};
+            if (q != 0)
+                ecgf::mul_xor_jt<1>(q, acc, y);
+            d = or_diff(d, syn + r * kScrubSlot, acc);
+        }
+        const uint64_t vote = __ballot(d != 0);
+        const u32 bit = __builtin_amdgcn_readfirstlane(packed_byte(a.bbrick, p));
+        if (t.cc == 0 && open && ((vote >> (t.cs * 16u)) & 0xFFFFu) == 0)
+            atomicOr(&t.flags[kScrubT + t.cs], 1u << bit);
+    }
+}
+
+/* the word of ec_method_locate for a stripe, from its two words: clean or
+ * one check brick, the basis brick, or MANY */
+__device__ __forceinline__ u32 locate_word(u32 f, u32 b)
+{
+    return (f & (f - 1u)) == 0 ? f : b ? b : kLocateMany;
+}
+
+/* the word of ec_method_locate2, from a stripe's three words: clean or one
+ * check brick, the basis brick, two check bricks, the pair, or MANY (a
+ * result of phase 3 that is not exactly two bits).  A word that a skipped
+ * phase did not touch is zero, so this holds on every path. */
+__device__ __forceinline__ u32 locate2_word(u32 f, u32 b, u32 w)
+{
+    const u32 nz = __builtin_popcount(f);
+    return nz <= 1 ? f : b ? b : nz == 2 ? f
+           : __builtin_popcount(w) == 2 ? w : kLocateMany;
+}
+
+/* The tile's final words to loc[], from its NF words per stripe, after the
+ * barrier of the last phase that ran.  CLEAN: the caller has just seen
+ * !scrub_dirty, so every word of the tile is zero and the final word is that
+ * of zeros, with no second trip to LDS at the end of the normal case (reading
+ * them there cost a clean 16+4 locate 1.4 to 2 % at 1 GiB per call). */
+template <u32 NF, bool CLEAN = false>
+__device__ __forceinline__ void scrub_store_loc(const ScrubTile &t, const LocateArgs &a)
+{
+    if (t.tid < kScrubT && t.t0 + t.tid < a.nstripes) {
+        u32 f = 0, b = 0, w = 0;
+        if constexpr (!CLEAN) {
+            f = t.flags[t.tid];
+            b = t.flags[kScrubT + t.tid];
+            if constexpr (NF == 3)
+                w = t.flags[2 * kScrubT + t.tid];
+        }
+        a.loc[t.t0 + t.tid] = NF == 3 ? locate2_word(f, b, w) : locate_word(f, b);
+    }
+}
+
+/* open for a pair: three or more non-zero rows and no single position
+ * (exactly two non-zero syndromes are those two check bricks: nothing to
+ * compute) */
+__device__ __forceinline__ bool pair_open(u32 f, u32 b)
+{
+    return __builtin_popcount(f) >= 3 && b == 0;
+}
+
+/* block-uniform, from LDS after phase 2's barrier: is a stripe of the tile
+ * open for a pair? */
+__device__ __forceinline__ bool scrub_wants_pairs(const ScrubTile &t)
+{
+    u32 need = 0;
+#pragma unroll
+    for (u32 s = 0; s < kScrubT; ++s)
+        need |= (u32)pair_open(t.flags[s], t.flags[kScrubT + s]);
+    return __builtin_amdgcn_readfirstlane(need) != 0;
+}
+
+/* Phase 3, for a tile with a stripe open for a pair: 2k + C(k, 2) candidates
+ * spread over the waves.
  *
  *   (p, ref 0)   s_r == q[r][p] * s_0 for the rows r >= 1.  Exactly one row
  *                that fails is the pair (basis p, that check brick): removing
@@ -1954,167 +1826,45 @@ struct Locate2Args {
  *                e_p ^ G[r][q] * e_q for the rows r >= 2: none failing is
  *                the pair of basis positions.
  *
- * All three are one loop over rows around one multiply site (the jump-table
- * multiply is ~50 KiB of code per site): a step XORs up to two products into
- * acc, then either keeps acc as e_p / e_q or compares it with s_r, the 16
- * lanes of a stripe voting by ballot.  Every choice in it is wave-uniform.
- * With a - k >= 4 at most one pair passes when no single brick does (two
- * would make two codewords that agree on k positions), so the bits are ORed
- * in LDS without ordering; a result that is not exactly two bits is MANY.
- * No barrier sits in a loop.  Each loc[t] leaves by one plain dword store. */
-template <int K, int NW, int LA = kLdsDmaDefault>
-__global__ __launch_bounds__(NW * 64) void ec_locate2_n(const Locate2Args a)
+ * All three are one loop over rows around one multiply site: a step XORs up
+ * to two products into acc, then either keeps acc as e_p / e_q or compares it
+ * with s_r, the 16 lanes of a stripe voting by ballot.  With a - k >= 4 at
+ * most one pair passes when no single brick does (two would make two
+ * codewords that agree on k positions), so the bits are ORed into
+ * flags[2T + s] without ordering. */
+template <int NW>
+__device__ __forceinline__ void scrub_pairs(const ScrubTile &t, const Locate2Args &a)
 {
-    constexpr u32 T = 4;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const u32 tid = threadIdx.x;
-    const u32 k = a.l.k, kw = a.l.kw, rows = a.l.rows, ni = k + rows;
-    const uint64_t t0 = (uint64_t)blockIdx.x * T;
-    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 lane = tid & 63u;
-    /* flags[s]: brick bits of stripe s's non-zero rows; flags[T + s]: the
-     * brick bit of the basis position that explains them; flags[2T + s]:
-     * the brick bits of the pair that does */
-    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
-    if (tid < 3 * T)
-        flags[tid] = 0;
-    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
-        return a.l.in[p] + st * ECD_CHUNK;
-    }, ni, t0, a.l.nstripes, wave, lane);
-    __syncthreads();
-    const u32 cs = lane >> 4, cc = lane & 15u;
-    uint8_t *col = lds + cs * 64u + cc * 4u;
-    const bool live = t0 + cs < a.l.nstripes;
-    for (u32 r = wave; r < rows; r += NW) {
-        const u32 rw = kw * r;
-        const u32 w0 = a.l.coef[rw];
-        const u32 w1 = K > 4 ? a.l.coef[rw + 1] : 0u;
-        const u32 w2 = K > 8 ? a.l.coef[rw + 2] : 0u;
-        const u32 w3 = K > 12 ? a.l.coef[rw + 3] : 0u;
-        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
-        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
-        u32 acc[8][1], y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            acc[b][0] = 0;
-#pragma unroll 1
-        for (u32 p = 0; p < k; ++p) {
-            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
-            cl = (cl >> 8) | (ch << 56);
-            ch >>= 8;
-            if (c == 0)
-                continue;
-            const uint8_t *src = col + p * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-            ecgf::mul_xor_jt<1>(c, acc, y);
-        }
-        /* the syndrome replaces the stored chunk in LDS */
-        uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
-        u32 d = 0;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (T * 64u));
-            const u32 s = acc[b][0] ^ *w;
-            *w = s;
-            d |= s;
-        }
-        const uint64_t vote = __ballot(live && d != 0);
-        const u32 brick = __builtin_amdgcn_readfirstlane((a.l.cbrick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
-        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
-            atomicOr(&flags[cs], 1u << brick);
-    }
-    __syncthreads();
-    const u32 any = __builtin_amdgcn_readfirstlane(flags[0] | flags[1] | flags[2] | flags[3]);
-    if (any == 0) {
-        if (tid < T && t0 + tid < a.l.nstripes)
-            a.l.loc[t0 + tid] = 0;
-        return;
-    }
-    /* a stripe with two or more non-zero rows looks for its basis position
-     * (stripes past nstripes have no flag) */
-    const u32 mine = flags[cs];
-    const bool open = (mine & (mine - 1u)) != 0;
-    const uint8_t *syn = col + k * (T * ECD_CHUNK);
-    for (u32 p = wave; p < k; p += NW) {
-        u32 y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            y[b][0] = *reinterpret_cast<const u32 *>(syn + (u32)b * (T * 64u));
-        u32 d = 0;
-#pragma unroll 1
-        for (u32 r = 1; r < rows; ++r) {
-            const u32 q = __builtin_amdgcn_readfirstlane(
-                (a.l.ratio[(r - 1) * kw + (p >> 2)] >> ((p & 3u) * 8u)) & 0xFFu);
-            u32 acc[8][1];
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                acc[b][0] = 0;
-            if (q != 0)
-                ecgf::mul_xor_jt<1>(q, acc, y);
-            const uint8_t *sr = syn + r * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
-        }
-        const uint64_t vote = __ballot(d != 0);
-        const u32 brick = __builtin_amdgcn_readfirstlane((a.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
-        if (cc == 0 && open && ((vote >> (cs * 16u)) & 0xFFFFu) == 0)
-            atomicOr(&flags[T + cs], 1u << brick);
-    }
-    __syncthreads();
-    /* open for a pair: three or more non-zero rows, no single position */
-    u32 need = 0;
-#pragma unroll
-    for (u32 s = 0; s < T; ++s)
-        need |= (u32)(__builtin_popcount(flags[s]) >= 3 && flags[T + s] == 0);
-    if (__builtin_amdgcn_readfirstlane(need) == 0) {
-        if (tid < T && t0 + tid < a.l.nstripes) {
-            const u32 f = flags[tid], b = flags[T + tid];
-            a.l.loc[t0 + tid] = __builtin_popcount(f) <= 1 ? f : b ? b : f;
-        }
-        return;
-    }
-    const bool open2 = __builtin_popcount(mine) >= 3 && flags[T + cs] == 0;
+    const u32 k = a.l.k, kw = a.l.kw, rows = a.l.rows;
+    const bool open2 = pair_open(t.flags[t.cs], t.flags[kScrubT + t.cs]);
+    const uint8_t *syn = t.col + k * kScrubSlot;
     const u32 nitems = 2u * k + a.npairs;
-    for (u32 it = wave; it < nitems; it += NW) {
+    for (u32 it = t.wave; it < nitems; it += NW) {
         /* wave-uniform: a basis pair (p, q), or position p against row ref */
         const bool pair = it >= 2u * k;
         const u32 pi = pair ? it - 2u * k : 0u;
-        const u32 pq = __builtin_amdgcn_readfirstlane((a.ppq[pi >> 2] >> ((pi & 3u) * 8u)) & 0xFFu);
+        const u32 pq = __builtin_amdgcn_readfirstlane(packed_byte(a.ppq, pi));
         const u32 inv = __builtin_amdgcn_readfirstlane(a.pinv[pi]);
         const u32 ref = pair ? 0u : it >= k ? 1u : 0u;
         const u32 p = pair ? pq >> 4 : it - ref * k;
         const u32 q = pq & 15u;
-        u32 ep[8][1], eq[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            ep[b][0] = eq[b][0] = 0;
+        u32 ep[8][1] = {}, eq[8][1] = {};
         u32 failed = 0;             /* rows of this lane's stripe that do not fit */
 #pragma unroll 1
         for (u32 st = pair ? 0u : ref + 1u; st < rows; ++st) {
             const bool solve = pair && st < 2u;
-            u32 acc[8][1], y[8][1];
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                acc[b][0] = 0;
+            u32 acc[8][1] = {}, y[8][1];
 #pragma unroll 1
             for (u32 j = 0; j < (pair ? 2u : 1u); ++j) {
                 u32 c;
                 if (!pair || solve) {
                     /* from LDS: s_ref, or s_0 and s_1 */
                     const u32 *tab = ref ? a.ratio1 : a.l.ratio;
-                    const u32 ri = pair ? 0u : (st - 1u - ref) * kw + (p >> 2);
-                    c = pair ? (inv >> ((2u * st + j) * 8u)) & 0xFFu
-                             : (tab[ri] >> ((p & 3u) * 8u)) & 0xFFu;
-                    const uint8_t *src = syn + (pair ? j : ref) * (T * ECD_CHUNK);
-#pragma unroll
-                    for (int b = 0; b < 8; ++b)
-                        y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
+                    const u32 ri = pair ? 0u : (st - 1u - ref) * kw;
+                    c = pair ? (inv >> ((2u * st + j) * 8u)) & 0xFFu : packed_byte(tab + ri, p);
+                    read_column(syn + (pair ? j : ref) * kScrubSlot, y);
                 } else {
-                    const u32 x = j ? q : p;
-                    c = (a.l.coef[st * kw + (x >> 2)] >> ((x & 3u) * 8u)) & 0xFFu;
+                    c = packed_byte(a.l.coef + st * kw, j ? q : p);
 #pragma unroll
                     for (int b = 0; b < 8; ++b)
                         y[b][0] = j ? eq[b][0] : ep[b][0];
@@ -2133,271 +1883,198 @@ __global__ __launch_bounds__(NW * 64) void ec_locate2_n(const Locate2Args a)
                 }
                 continue;
             }
-            const uint8_t *sr = syn + st * (T * ECD_CHUNK);
-            u32 d = 0;
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
+            const u32 d = or_diff(0, syn + st * kScrubSlot, acc);
             const uint64_t vote = __ballot(d != 0);
-            if (((vote >> (cs * 16u)) & 0xFFFFu) != 0)
+            if (((vote >> (t.cs * 16u)) & 0xFFFFu) != 0)
                 failed |= 1u << st;
         }
         /* (p, ref 0): the one failing row is the pair's check brick;
          * otherwise nothing may fail, and the second brick is row 0's, or q's */
         const bool one = !pair && ref == 0;
         const bool pass = one ? __builtin_popcount(failed) == 1 : failed == 0;
-        if (cc == 0 && open2 && pass) {
+        if (t.cc == 0 && open2 && pass) {
             const u32 cr = one ? (u32)__builtin_ctz(failed) : 0u;
-            const u32 b0 = (a.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu;
-            const u32 b1 = pair ? (a.l.bbrick[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu
-                                : (a.l.cbrick[cr >> 2] >> ((cr & 3u) * 8u)) & 0xFFu;
-            atomicOr(&flags[2 * T + cs], (1u << b0) | (1u << b1));
+            const u32 b0 = packed_byte(a.l.bbrick, p);
+            const u32 b1 = pair ? packed_byte(a.l.bbrick, q) : packed_byte(a.l.cbrick, cr);
+            atomicOr(&t.flags[2 * kScrubT + t.cs], (1u << b0) | (1u << b1));
         }
     }
-    __syncthreads();
-    if (tid < T && t0 + tid < a.l.nstripes) {
-        const u32 f = flags[tid], b = flags[T + tid], w = flags[2 * T + tid];
-        const u32 nz = __builtin_popcount(f);
-        a.l.loc[t0 + tid] = nz <= 1 ? f : b ? b : nz == 2 ? f
-                            : __builtin_popcount(w) == 2 ? w : kLocateMany;
+}
+
+/* The decode of the tile's (corrected) basis slots: the k output rows are
+ * spread over the waves like the check rows of phase 1; row j is the sum of
+ * inv(B)[j][p] * x_p over the basis slots and leaves by dword stores, 64
+ * contiguous bytes per plane and stripe (stripe t at out + t * k * 512). */
+template <int K, int NW>
+__device__ __forceinline__ void scrub_decode(const ScrubTile &t, const u32 *inv, u32 k, u32 kw,
+                                             uint8_t *out)
+{
+    uint8_t *o = out + (t.t0 + t.cs) * ((uint64_t)k * ECD_CHUNK) + t.cc * 4u;
+    for (u32 j = t.wave; j < k; j += NW) {
+        u32 acc[8][1];
+        row_product<K>(inv, j, kw, k, t.col, acc);
+        if (t.live)
+            store_chunk<1, true>(o + j * ECD_CHUNK, acc);
     }
 }
 
-/* dynamic LDS of an ec_locate2_n launch: the tile and three words per stripe */
-constexpr size_t locate2_n_lds(u32 inputs)
+/* ---------------------------------------------- scrub: the five tile kernels */
+
+/* ec_method_verify_device: do the stored fragments of `rows` bricks agree
+ * with what the k basis fragments imply?  Phase 1 alone, with one word per
+ * stripe and the stored chunks left as they are: bad[t] is flags[s]. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_verify_n(const VerifyArgs a)
 {
-    return (size_t)inputs * 4 * ECD_CHUNK + 12 * sizeof(u32);
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    ScrubTile t = scrub_stage<1, NW, LA>(lds, a);
+    __syncthreads();
+    scrub_place(t, lds, a.nstripes);
+    scrub_syndromes<K, NW, false>(t, a.coef, a.brick, a.k, a.kw, a.rows);
+    __syncthreads();
+    if (t.tid < kScrubT && t.t0 + t.tid < a.nstripes)
+        a.bad[t.t0 + t.tid] = t.flags[t.tid];
 }
 
-/* ------------------------------------- a read that corrects up to two chunks */
-
-/* Kernel arguments of ec_decode_checked2_n: Locate2Args, then the decoded
- * output (stripe t at out + t * k * 512, any byte alignment), B as a brick
- * mask, inv(B) laid out like the coefficients (row j at word j * kw) and the
- * k bytes 1 / G[0][p] (ginv[0 ..]) and 1 / G[1][p] (ginv[ECD_MAX_K / 4 ..]).
- * 2,016 bytes in all. */
-struct DecodeChecked2Args {
-    Locate2Args l2;
-    uint8_t *out;
-    u32 bmask, pad;
-    u32 inv[ECD_MAX_K * (ECD_MAX_K / 4)];
-    u32 ginv[2 * (ECD_MAX_K / 4)];
-};
-
-/* the word of ec_locate2_n's last statement, from a stripe's three words */
-__device__ __forceinline__ u32 locate2_word(u32 f, u32 b, u32 w)
+/* ec_method_locate_device: which brick's chunk is wrong?  Phase 1 keeps the
+ * syndromes; a tile whose four flags are zero stores four zeros and is done,
+ * the normal case, at verify's cost plus the write-back.  A tile with a dirty
+ * stripe runs phase 2. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_locate_n(const LocateArgs a)
 {
-    const u32 nz = __builtin_popcount(f);
-    return nz <= 1 ? f : b ? b : nz == 2 ? f
-           : __builtin_popcount(w) == 2 ? w : kLocateMany;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    ScrubTile t = scrub_stage<2, NW, LA>(lds, a);
+    __syncthreads();
+    scrub_place(t, lds, a.nstripes);
+    scrub_syndromes<K, NW, true>(t, a.coef, a.cbrick, a.k, a.kw, a.rows);
+    __syncthreads();
+    if (!scrub_dirty(t)) {
+        scrub_store_loc<2, true>(t, a);
+        return;
+    }
+    scrub_single<NW>(t, a);
+    __syncthreads();
+    scrub_store_loc<2>(t, a);
+}
+
+/* ec_method_locate2_device: which one or two bricks' chunks are wrong?
+ * ec_locate_n with a third word per stripe.  After phase 2 a stripe is still
+ * open when three or more syndromes are non-zero and no basis position
+ * passed; a tile without one stores its four words and is done, and only a
+ * tile with one runs phase 3. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_locate2_n(const Locate2Args a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 k = a.l.k, kw = a.l.kw, rows = a.l.rows;
+    ScrubTile t = scrub_stage<3, NW, LA>(lds, a.l);
+    __syncthreads();
+    scrub_place(t, lds, a.l.nstripes);
+    scrub_syndromes<K, NW, true>(t, a.l.coef, a.l.cbrick, k, kw, rows);
+    __syncthreads();
+    if (!scrub_dirty(t)) {
+        scrub_store_loc<3, true>(t, a.l);
+        return;
+    }
+    scrub_single<NW>(t, a.l);
+    __syncthreads();
+    if (!scrub_wants_pairs(t)) {
+        scrub_store_loc<3>(t, a.l);
+        return;
+    }
+    scrub_pairs<NW>(t, a);
+    __syncthreads();
+    scrub_store_loc<3>(t, a.l);
+}
+
+/* ec_method_decode_checked_device: decode the k lowest bricks and, in the
+ * same pass, check them against the others and correct a single bad chunk:
+ * ec_locate_n's phases, a correction in LDS, the dense decode.  A clean tile
+ * skips phase 2 and the correction.
+ *
+ * The correction, for a stripe whose result word names basis position p: the
+ * error in p is e = s_0 / G[0][p] (s_0 = G[0][p] * e when p alone is wrong),
+ * and XORing e into p's LDS slot puts the basis chunks on the one codeword
+ * the other a - 1 chunks lie on, so that one dense decode with inv(B) gives
+ * what inv(B_i) would give from the undamaged chunks.  The coefficient must
+ * be wave-uniform and p differs per stripe: the tile's four stripes go one
+ * per wave item, each on its own 16 lanes, around one multiply site.  MANY
+ * stripes, check-brick stripes and stripes past nstripes are left alone. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_decode_checked_n(const DecodeCheckedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 k = a.l.k;
+    ScrubTile t = scrub_stage<2, NW, LA>(lds, a.l);
+    __syncthreads();
+    scrub_place(t, lds, a.l.nstripes);
+    scrub_syndromes<K, NW, true>(t, a.l.coef, a.l.cbrick, k, a.l.kw, a.l.rows);
+    __syncthreads();
+    if (scrub_dirty(t)) {
+        scrub_single<NW>(t, a.l);
+        __syncthreads();
+        /* stripe s of the tile, on lanes 16 s .. 16 s + 15 of one wave: its
+         * words are final, and a named basis brick is the one bit of the
+         * second while the first has two or more (0 for stripes past
+         * nstripes).  c = 0 (nothing to correct) multiplies to zero. */
+        const uint8_t *s0 = t.col + k * kScrubSlot;
+        for (u32 s = t.wave; s < kScrubT; s += NW) {
+            const u32 f = __builtin_amdgcn_readfirstlane(t.flags[s]);
+            const u32 bb = __builtin_amdgcn_readfirstlane(t.flags[kScrubT + s]);
+            const bool fix = (f & (f - 1u)) != 0 && bb != 0;
+            const u32 p = fix ? (u32)__builtin_popcount(a.bmask & (bb - 1u)) : 0u;
+            const u32 c = __builtin_amdgcn_readfirstlane(fix ? packed_byte(a.ginv, p) : 0u);
+            if (c == 0)
+                continue;
+            u32 acc[8][1] = {}, y[8][1];
+            read_column(s0, y);
+            ecgf::mul_xor_jt<1>(c, acc, y);
+            if (t.cs == s)
+                xor_column(t.col + p * kScrubSlot, acc);
+        }
+        __syncthreads();
+    }
+    scrub_decode<K, NW>(t, a.inv, k, a.l.kw, a.out);
+    scrub_store_loc<2>(t, a.l);
 }
 
 /* ec_method_decode_checked2_device: decode the k lowest bricks and, in the
- * same pass, check them against the others and correct up to two bad chunks.
- * Phases 1 to 3 are ec_locate2_n's, statement for statement: the tile, the
- * syndromes left in the check chunks' LDS slots, the three words per stripe.
- * Its two early returns are ifs here: a clean tile skips phases 2 and 3 and
- * the correction, a tile without an open stripe skips phase 3.  Words phase 3
- * did not touch are zero, so one expression (locate2_word) gives the final
- * word W of a stripe on every path.
+ * same pass, check them against the others and correct up to two bad chunks:
+ * ec_locate2_n's phases, a correction in LDS, the dense decode.  ec_locate2_n's
+ * two early returns are ifs here: a clean tile skips phases 2 and 3 and the
+ * correction, a tile without an open stripe skips phase 3.
  *
- * The correction, for a stripe whose W names one or two basis positions (the
- * a - |S| other chunks lie on one codeword; its basis part is the stored basis
- * with an error XORed into each named position):
+ * The correction, for a stripe whose final word W names one or two basis
+ * positions (the a - |S| other chunks lie on one codeword; its basis part is
+ * the stored basis with an error XORed into each named position):
  *   p alone, or p and a check row c   e_p = s_ref / G[ref][p], ref = 0, or 1
  *                                     when c is row 0 (rows >= 4: row 1 is
  *                                     intact then);
  *   p < q                             e_p = a s_0 ^ b s_1, e_q = c s_0 ^ d s_1,
  *                                     {a, b, c, d} = pinv of the pair.
  * That is at most four terms (coefficient, s_0 or s_1, slot), one loop around
- * one multiply site.  The jump-table multiply wants a wave-uniform
- * coefficient: the tile's four stripes go one per wave item, each on its own
- * 16 lanes.  MANY stripes, check-only stripes and stripes past nstripes
- * (W = 0) are left alone.  After it one dense decode with inv(B) gives what
- * inv(B_S) would give from the undamaged chunks, as in ec_decode_checked_n.
- * No barrier sits in a loop, and every decision around one is read from LDS
- * after a barrier, so the whole block takes it together. */
+ * one multiply site, the tile's four stripes one per wave item as in
+ * ec_decode_checked_n.  MANY stripes, check-only stripes and stripes past
+ * nstripes (W = 0) are left alone.  After it one dense decode with inv(B)
+ * gives what inv(B_S) would give from the undamaged chunks. */
 template <int K, int NW, int LA = kLdsDmaDefault>
 __global__ __launch_bounds__(NW * 64) void ec_decode_checked2_n(const DecodeChecked2Args a)
 {
-    constexpr u32 T = 4;
-    static_assert(NW >= (int)T, "a wave per stripe of the tile");
+    static_assert(NW >= (int)kScrubT, "a wave per stripe of the tile");
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const u32 tid = threadIdx.x;
-    const u32 k = a.l2.l.k, kw = a.l2.l.kw, rows = a.l2.l.rows, ni = k + rows;
-    const uint64_t t0 = (uint64_t)blockIdx.x * T;
-    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const u32 lane = tid & 63u;
-    /* flags[s], flags[T + s], flags[2T + s]: as in ec_locate2_n */
-    u32 *flags = reinterpret_cast<u32 *>(lds + ni * (T * ECD_CHUNK));
-    if (tid < 3 * T)
-        flags[tid] = 0;
-    stage_tile<T, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
-        return a.l2.l.in[p] + st * ECD_CHUNK;
-    }, ni, t0, a.l2.l.nstripes, wave, lane);
+    const LocateArgs &l = a.l2.l;
+    const u32 k = l.k, kw = l.kw, rows = l.rows;
+    ScrubTile t = scrub_stage<3, NW, LA>(lds, l);
     __syncthreads();
-    const u32 cs = lane >> 4, cc = lane & 15u;
-    uint8_t *col = lds + cs * 64u + cc * 4u;
-    const bool live = t0 + cs < a.l2.l.nstripes;
-    for (u32 r = wave; r < rows; r += NW) {
-        const u32 rw = kw * r;
-        const u32 w0 = a.l2.l.coef[rw];
-        const u32 w1 = K > 4 ? a.l2.l.coef[rw + 1] : 0u;
-        const u32 w2 = K > 8 ? a.l2.l.coef[rw + 2] : 0u;
-        const u32 w3 = K > 12 ? a.l2.l.coef[rw + 3] : 0u;
-        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
-        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
-        u32 acc[8][1], y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            acc[b][0] = 0;
-#pragma unroll 1
-        for (u32 p = 0; p < k; ++p) {
-            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
-            cl = (cl >> 8) | (ch << 56);
-            ch >>= 8;
-            if (c == 0)
-                continue;
-            const uint8_t *src = col + p * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-            ecgf::mul_xor_jt<1>(c, acc, y);
-        }
-        /* the syndrome replaces the stored chunk in LDS */
-        uint8_t *chk = col + (k + r) * (T * ECD_CHUNK);
-        u32 d = 0;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            u32 *w = reinterpret_cast<u32 *>(chk + (u32)b * (T * 64u));
-            const u32 s = acc[b][0] ^ *w;
-            *w = s;
-            d |= s;
-        }
-        const uint64_t vote = __ballot(live && d != 0);
-        const u32 brick = __builtin_amdgcn_readfirstlane((a.l2.l.cbrick[r >> 2] >> ((r & 3u) * 8u)) & 0xFFu);
-        if (cc == 0 && ((vote >> (cs * 16u)) & 0xFFFFu) != 0)
-            atomicOr(&flags[cs], 1u << brick);
-    }
+    scrub_place(t, lds, l.nstripes);
+    scrub_syndromes<K, NW, true>(t, l.coef, l.cbrick, k, kw, rows);
     __syncthreads();
-    const uint8_t *syn = col + k * (T * ECD_CHUNK);
-    const u32 any = __builtin_amdgcn_readfirstlane(flags[0] | flags[1] | flags[2] | flags[3]);
-    if (any != 0) {
-        /* a stripe with two or more non-zero rows looks for its basis position
-         * (stripes past nstripes have no flag) */
-        const u32 mine = flags[cs];
-        const bool open = (mine & (mine - 1u)) != 0;
-        for (u32 p = wave; p < k; p += NW) {
-            u32 y[8][1];
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(syn + (u32)b * (T * 64u));
-            u32 d = 0;
-#pragma unroll 1
-            for (u32 r = 1; r < rows; ++r) {
-                const u32 q = __builtin_amdgcn_readfirstlane(
-                    (a.l2.l.ratio[(r - 1) * kw + (p >> 2)] >> ((p & 3u) * 8u)) & 0xFFu);
-                u32 acc[8][1];
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    acc[b][0] = 0;
-                if (q != 0)
-                    ecgf::mul_xor_jt<1>(q, acc, y);
-                const uint8_t *sr = syn + r * (T * ECD_CHUNK);
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
-            }
-            const uint64_t vote = __ballot(d != 0);
-            const u32 brick = __builtin_amdgcn_readfirstlane((a.l2.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
-            if (cc == 0 && open && ((vote >> (cs * 16u)) & 0xFFFFu) == 0)
-                atomicOr(&flags[T + cs], 1u << brick);
-        }
+    if (scrub_dirty(t)) {
+        scrub_single<NW>(t, l);
         __syncthreads();
-        /* open for a pair: three or more non-zero rows, no single position */
-        u32 need = 0;
-#pragma unroll
-        for (u32 s = 0; s < T; ++s)
-            need |= (u32)(__builtin_popcount(flags[s]) >= 3 && flags[T + s] == 0);
-        if (__builtin_amdgcn_readfirstlane(need) != 0) {
-            const bool open2 = __builtin_popcount(mine) >= 3 && flags[T + cs] == 0;
-            const u32 nitems = 2u * k + a.l2.npairs;
-            for (u32 it = wave; it < nitems; it += NW) {
-                /* wave-uniform: a basis pair (p, q), or position p against row ref */
-                const bool pair = it >= 2u * k;
-                const u32 pi = pair ? it - 2u * k : 0u;
-                const u32 pq = __builtin_amdgcn_readfirstlane((a.l2.ppq[pi >> 2] >> ((pi & 3u) * 8u)) & 0xFFu);
-                const u32 inv = __builtin_amdgcn_readfirstlane(a.l2.pinv[pi]);
-                const u32 ref = pair ? 0u : it >= k ? 1u : 0u;
-                const u32 p = pair ? pq >> 4 : it - ref * k;
-                const u32 q = pq & 15u;
-                u32 ep[8][1], eq[8][1];
-#pragma unroll
-                for (int b = 0; b < 8; ++b)
-                    ep[b][0] = eq[b][0] = 0;
-                u32 failed = 0;         /* rows of this lane's stripe that do not fit */
-#pragma unroll 1
-                for (u32 st = pair ? 0u : ref + 1u; st < rows; ++st) {
-                    const bool solve = pair && st < 2u;
-                    u32 acc[8][1], y[8][1];
-#pragma unroll
-                    for (int b = 0; b < 8; ++b)
-                        acc[b][0] = 0;
-#pragma unroll 1
-                    for (u32 j = 0; j < (pair ? 2u : 1u); ++j) {
-                        u32 c;
-                        if (!pair || solve) {
-                            /* from LDS: s_ref, or s_0 and s_1 */
-                            const u32 *tab = ref ? a.l2.ratio1 : a.l2.l.ratio;
-                            const u32 ri = pair ? 0u : (st - 1u - ref) * kw + (p >> 2);
-                            c = pair ? (inv >> ((2u * st + j) * 8u)) & 0xFFu
-                                     : (tab[ri] >> ((p & 3u) * 8u)) & 0xFFu;
-                            const uint8_t *src = syn + (pair ? j : ref) * (T * ECD_CHUNK);
-#pragma unroll
-                            for (int b = 0; b < 8; ++b)
-                                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-                        } else {
-                            const u32 x = j ? q : p;
-                            c = (a.l2.l.coef[st * kw + (x >> 2)] >> ((x & 3u) * 8u)) & 0xFFu;
-#pragma unroll
-                            for (int b = 0; b < 8; ++b)
-                                y[b][0] = j ? eq[b][0] : ep[b][0];
-                        }
-                        c = __builtin_amdgcn_readfirstlane(c);
-                        if (c != 0)
-                            ecgf::mul_xor_jt<1>(c, acc, y);
-                    }
-                    if (solve) {
-#pragma unroll
-                        for (int b = 0; b < 8; ++b) {
-                            if (st == 0)
-                                ep[b][0] = acc[b][0];
-                            else
-                                eq[b][0] = acc[b][0];
-                        }
-                        continue;
-                    }
-                    const uint8_t *sr = syn + st * (T * ECD_CHUNK);
-                    u32 d = 0;
-#pragma unroll
-                    for (int b = 0; b < 8; ++b)
-                        d |= acc[b][0] ^ *reinterpret_cast<const u32 *>(sr + (u32)b * (T * 64u));
-                    const uint64_t vote = __ballot(d != 0);
-                    if (((vote >> (cs * 16u)) & 0xFFFFu) != 0)
-                        failed |= 1u << st;
-                }
-                /* (p, ref 0): the one failing row is the pair's check brick;
-                 * otherwise nothing may fail, and the second brick is row 0's, or q's */
-                const bool one = !pair && ref == 0;
-                const bool pass = one ? __builtin_popcount(failed) == 1 : failed == 0;
-                if (cc == 0 && open2 && pass) {
-                    const u32 cr = one ? (u32)__builtin_ctz(failed) : 0u;
-                    const u32 b0 = (a.l2.l.bbrick[p >> 2] >> ((p & 3u) * 8u)) & 0xFFu;
-                    const u32 b1 = pair ? (a.l2.l.bbrick[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu
-                                        : (a.l2.l.cbrick[cr >> 2] >> ((cr & 3u) * 8u)) & 0xFFu;
-                    atomicOr(&flags[2 * T + cs], (1u << b0) | (1u << b1));
-                }
-            }
+        if (scrub_wants_pairs(t)) {
+            scrub_pairs<NW>(t, a.l2);
             __syncthreads();
         }
         /* stripe s of the tile, on lanes 16 s .. 16 s + 15 of one wave: its
@@ -2405,75 +2082,36 @@ __global__ __launch_bounds__(NW * 64) void ec_decode_checked2_n(const DecodeChec
          * only, MANY, past nstripes) leaves the stripe alone; one is position
          * p, with s_0, or with s_1 when W's other bit is the brick of check
          * row 0; two are p < q with the four bytes of their pinv. */
-        for (u32 s = wave; s < T; s += NW) {
+        const uint8_t *syn = t.col + k * kScrubSlot;
+        for (u32 s = t.wave; s < kScrubT; s += NW) {
             const u32 w = __builtin_amdgcn_readfirstlane(
-                locate2_word(flags[s], flags[T + s], flags[2 * T + s]));
+                locate2_word(t.flags[s], t.flags[kScrubT + s], t.flags[2 * kScrubT + s]));
             const u32 wb = w & a.bmask;
             if (wb == 0)
                 continue;
             const bool two = (wb & (wb - 1u)) != 0;
             const u32 p = (u32)__builtin_popcount(a.bmask & ((wb & (0u - wb)) - 1u));
             const u32 q = (u32)__builtin_popcount(a.bmask & ((wb & (wb - 1u)) - 1u));
-            const u32 ref = !two && (w ^ wb) == 1u << (a.l2.l.cbrick[0] & 0xFFu) ? 1u : 0u;
-            const u32 gi = ref * (ECD_MAX_K / 4) + (p >> 2);
+            const u32 ref = !two && (w ^ wb) == 1u << packed_byte(l.cbrick, 0) ? 1u : 0u;
             const u32 cw = two ? a.l2.pinv[p * (2u * k - p - 1u) / 2u + q - p - 1u]
-                               : (a.ginv[gi] >> ((p & 3u) * 8u)) & 0xFFu;
+                               : packed_byte(a.ginv + ref * (ECD_MAX_K / 4), p);
             const u32 nterms = two ? 4u : 1u;
 #pragma unroll 1
             for (u32 i = 0; i < nterms; ++i) {
                 const u32 c = __builtin_amdgcn_readfirstlane((cw >> (i * 8u)) & 0xFFu);
                 if (c == 0)
                     continue;
-                const uint8_t *src = syn + (two ? i & 1u : ref) * (T * ECD_CHUNK);
-                u32 acc[8][1], y[8][1];
-#pragma unroll
-                for (int b = 0; b < 8; ++b) {
-                    acc[b][0] = 0;
-                    y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-                }
+                u32 acc[8][1] = {}, y[8][1];
+                read_column(syn + (two ? i & 1u : ref) * kScrubSlot, y);
                 ecgf::mul_xor_jt<1>(c, acc, y);
-                if (cs == s) {
-                    uint8_t *x = col + (i < 2u ? p : q) * (T * ECD_CHUNK);
-#pragma unroll
-                    for (int b = 0; b < 8; ++b)
-                        *reinterpret_cast<u32 *>(x + (u32)b * (T * 64u)) ^= acc[b][0];
-                }
+                if (t.cs == s)
+                    xor_column(t.col + (i < 2u ? p : q) * kScrubSlot, acc);
             }
         }
         __syncthreads();
     }
-    /* the decode of the (corrected) basis chunks */
-    uint8_t *o = a.out + (t0 + cs) * ((uint64_t)k * ECD_CHUNK) + cc * 4u;
-    for (u32 j = wave; j < k; j += NW) {
-        const u32 rw = kw * j;
-        const u32 w0 = a.inv[rw];
-        const u32 w1 = K > 4 ? a.inv[rw + 1] : 0u;
-        const u32 w2 = K > 8 ? a.inv[rw + 2] : 0u;
-        const u32 w3 = K > 12 ? a.inv[rw + 3] : 0u;
-        uint64_t cl = (uint64_t)w0 | ((uint64_t)w1 << 32);
-        uint64_t ch = (uint64_t)w2 | ((uint64_t)w3 << 32);
-        u32 acc[8][1], y[8][1];
-#pragma unroll
-        for (int b = 0; b < 8; ++b)
-            acc[b][0] = 0;
-#pragma unroll 1
-        for (u32 p = 0; p < k; ++p) {
-            const u32 c = __builtin_amdgcn_readfirstlane((u32)cl & 0xFFu);
-            cl = (cl >> 8) | (ch << 56);
-            ch >>= 8;
-            if (c == 0)
-                continue;
-            const uint8_t *src = col + p * (T * ECD_CHUNK);
-#pragma unroll
-            for (int b = 0; b < 8; ++b)
-                y[b][0] = *reinterpret_cast<const u32 *>(src + (u32)b * (T * 64u));
-            ecgf::mul_xor_jt<1>(c, acc, y);
-        }
-        if (live)
-            store_chunk<1, true>(o + j * ECD_CHUNK, acc);
-    }
-    if (tid < T && t0 + tid < a.l2.l.nstripes)
-        a.l2.l.loc[t0 + tid] = locate2_word(flags[tid], flags[T + tid], flags[2 * T + tid]);
+    scrub_decode<K, NW>(t, a.inv, k, l.kw, a.out);
+    scrub_store_loc<3>(t, l);
 }
 
 /* ------------------------------------------- repairing the named chunks */
@@ -2495,16 +2133,46 @@ struct RepairArgs {
 
 constexpr u32 kRepairThreads = 256;
 
+/* One step of the repair kernels' scan of a wave's 64 loc words (w: this
+ * lane's, base: the stripe of lane 0).  Take the word of the first lane in
+ * `dirty`, then up to four dirty stripes that hold the same word, so that
+ * every coefficient that follows is wave-uniform, and clear them from the
+ * set: 16 lanes per stripe, each lane one dword column of the 8 planes (the
+ * layout of the tile kernels), at byte offset `off` of every fragment.  Lanes
+ * of a group without a stripe are not live. */
+struct RepairPick {
+    u32 wf;             /* the word, wave-uniform */
+    bool live;
+    uint64_t off;
+};
+
+__device__ __forceinline__ RepairPick repair_pick(uint64_t &dirty, u32 w, uint64_t base, u32 lane)
+{
+    const u32 first = __builtin_amdgcn_readfirstlane((u32)__builtin_ctzll(dirty));
+    const u32 wf = __builtin_amdgcn_readlane(w, first);
+    const uint64_t same = __ballot(w == wf) & dirty;
+    uint64_t rest = same;
+    u32 sel[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        sel[g] = rest ? (u32)__builtin_ctzll(rest) : 64u;
+        rest &= rest - 1u;
+    }
+    dirty &= ~(same ^ rest);
+    const u32 grp = lane >> 4, cc = lane & 15u;
+    const u32 src = grp == 0 ? sel[0] : grp == 1 ? sel[1] : grp == 2 ? sel[2] : sel[3];
+    return {wf, src < 64u, (base + src) * ECD_CHUNK + cc * 4u};
+}
+
 /* ec_method_repair_device: rewrite the chunks loc[] names.  The work is
  * sparse, so there is no tile: the grid strides over loc[], each lane of a
  * wave reads one word and the ballot of "one bit, of a brick in avail" is
  * the wave's dirty set, empty in the normal case.  The jump-table multiply
  * wants a wave-uniform coefficient, so the wave takes the brick of its first
- * dirty lane and up to four dirty stripes of its 64 that name that brick: 16
- * lanes per stripe, each lane one dword column of the 8 planes (the layout of
- * ec_locate_n), straight from global memory at byte addresses (gfx950 runs in
- * unaligned access mode, see load_plane_unaligned).  It clears those bits and
- * loops until the set is empty.  Every stripe belongs to one wave, and the
+ * dirty lane and up to four dirty stripes of its 64 that name that brick
+ * (repair_pick), straight from global memory at byte addresses (gfx950 runs
+ * in unaligned access mode, see load_plane_unaligned), and loops until the
+ * set is empty.  Every stripe belongs to one wave, and the
  * named chunk is written and never read (B_i excludes i): no LDS, no barrier,
  * no atomics.  Every branch around the multiply is wave-uniform; only the
  * loads and stores are predicated by `live`. */
@@ -2512,7 +2180,6 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair_n(const RepairArgs a
 {
     const u32 lane = threadIdx.x & 63u;
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const u32 grp = lane >> 4, cc = lane & 15u;
     const u32 k = a.k;
     const uint64_t step = (uint64_t)gridDim.x * kRepairThreads;
     for (uint64_t base = ((uint64_t)blockIdx.x * (kRepairThreads / 64u) + wave) * 64u;
@@ -2522,22 +2189,9 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair_n(const RepairArgs a
         /* MANY is bit 31 and avail has no bit at or above n <= 31 */
         uint64_t dirty = __ballot(w != 0 && (w & (w - 1u)) == 0 && (w & a.avail) != 0);
         while (dirty != 0) {
-            const u32 first = __builtin_amdgcn_readfirstlane((u32)__builtin_ctzll(dirty));
-            const u32 wf = __builtin_amdgcn_readlane(w, first);
+            /* up to four stripes of the set that name one brick */
+            const auto [wf, live, off] = repair_pick(dirty, w, base, lane);
             const u32 brick = __builtin_amdgcn_readfirstlane((u32)__builtin_ctz(wf));
-            /* up to four stripes of the set that name this brick */
-            const uint64_t same = __ballot(w == wf) & dirty;
-            uint64_t rest = same;
-            u32 sel[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                sel[g] = rest ? (u32)__builtin_ctzll(rest) : 64u;
-                rest &= rest - 1u;
-            }
-            dirty &= ~(same ^ rest);
-            const u32 src = grp == 0 ? sel[0] : grp == 1 ? sel[1] : grp == 2 ? sel[2] : sel[3];
-            const bool live = src < 64u;
-            const uint64_t off = (base + src) * ECD_CHUNK + cc * 4u;
             /* position of the brick in B (k: a check brick); input p of B_i
              * is entry p of bset, skipping that position */
             const u32 j = (a.bmask >> brick) & 1u ? (u32)__builtin_popcount(a.bmask & ((1u << brick) - 1u))
@@ -2554,7 +2208,7 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair_n(const RepairArgs a
                 cl = (cl >> 8) | (ch << 56);
                 ch >>= 8;
                 const u32 q = p + (p >= j ? 1u : 0u);
-                const u32 sb = __builtin_amdgcn_readfirstlane((a.bset[q >> 2] >> ((q & 3u) * 8u)) & 0xFFu);
+                const u32 sb = __builtin_amdgcn_readfirstlane(packed_byte(a.bset, q));
                 const uint8_t *in = a.frag[sb];
 #pragma unroll
                 for (int b = 0; b < 8; ++b)
@@ -2606,9 +2260,8 @@ struct Repair2Args {
  * scan is ec_repair_n's: the grid strides over loc[], a lane per word, and the
  * ballot of "one or two bits, all of bricks in avail" is the wave's dirty set,
  * empty in the normal case.  The wave takes the word of its first dirty lane
- * and up to four dirty stripes of its 64 that hold the same word (so that
- * every coefficient is wave-uniform), 16 lanes per stripe, a dword column of
- * the 8 planes per lane, at byte addresses; it clears those bits and loops.
+ * and up to four dirty stripes of its 64 that hold the same word (repair_pick),
+ * at byte addresses, and loops.
  *
  * There is no row per pair (C(31, 2) pairs would not fit the arguments): the
  * named set S is rebuilt through the syndromes of the check rows against B,
@@ -2629,7 +2282,7 @@ struct Repair2Args {
  * bytes of E * inv(B_S), as GF(2^8) has no rounding.  One brick named alone
  * goes the same way (one syndrome, or one prediction) and gets the bytes of
  * ec_repair_n.  All passes are one loop around one multiply site (the
- * jump-table multiply is ~50 KiB of code per site), every choice in it
+ * jump-table multiply is ~26 KiB of code per site), every choice in it
  * wave-uniform; only loads and stores are predicated by `live`.
  *
  * Unlike in ec_repair_n, a written chunk may have been read before (a basis
@@ -2640,7 +2293,6 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair2_n(const Repair2Args
 {
     const u32 lane = threadIdx.x & 63u;
     const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const u32 grp = lane >> 4, cc = lane & 15u;
     const u32 k = a.k, kw = a.kw;
     const u32 cmask = a.avail & ~a.bmask;
     const uint64_t step = (uint64_t)gridDim.x * kRepairThreads;
@@ -2651,21 +2303,8 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair2_n(const Repair2Args
         /* MANY is bit 31 and avail has no bit at or above n <= 31 */
         uint64_t dirty = __ballot(w != 0 && __builtin_popcount(w) <= 2 && (w & ~a.avail) == 0);
         while (dirty != 0) {
-            const u32 first = __builtin_amdgcn_readfirstlane((u32)__builtin_ctzll(dirty));
-            const u32 wf = __builtin_amdgcn_readlane(w, first);
-            /* up to four stripes of the set that hold this word */
-            const uint64_t same = __ballot(w == wf) & dirty;
-            uint64_t rest = same;
-            u32 sel[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                sel[g] = rest ? (u32)__builtin_ctzll(rest) : 64u;
-                rest &= rest - 1u;
-            }
-            dirty &= ~(same ^ rest);
-            const u32 src = grp == 0 ? sel[0] : grp == 1 ? sel[1] : grp == 2 ? sel[2] : sel[3];
-            const bool live = src < 64u;
-            const uint64_t off = (base + src) * ECD_CHUNK + cc * 4u;
+            /* up to four stripes of the set that hold one word */
+            const auto [wf, live, off] = repair_pick(dirty, w, base, lane);
             /* S: nb basis positions p < q and nc check rows r0 < r1 (basis
              * bricks are below check bricks, so the low bit is p's if any) */
             const u32 sb = wf & a.bmask, sc = wf & cmask;
@@ -2679,7 +2318,7 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair2_n(const Repair2Args
             const u32 pi = nb == 2 ? p * (2u * k - p - 1u) / 2u + (q - p - 1u) : 0u;
             /* the solve coefficients {a, b, c, d}; one position: {1 / G[ref][p]} */
             const u32 inv = __builtin_amdgcn_readfirstlane(
-                nb == 2 ? a.pinv[pi] : (a.ginv[ref][p >> 2] >> ((p & 3u) * 8u)) & 0xFFu);
+                nb == 2 ? a.pinv[pi] : packed_byte(a.ginv[ref], p));
             u32 s0[8][1], s1[8][1], f0[8][1], f1[8][1];
 #pragma unroll
             for (int b = 0; b < 8; ++b)
@@ -2704,7 +2343,7 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair2_n(const Repair2Args
                         for (int b = 0; b < 8; ++b)
                             y[b][0] = tm ? s1[b][0] : s0[b][0];
                     } else {
-                        c = (a.g[row * kw + (tm >> 2)] >> ((tm & 3u) * 8u)) & 0xFFu;
+                        c = packed_byte(a.g + row * kw, tm);
                         const bool fix0 = !syn && nb >= 1 && tm == p;
                         const bool fix1 = !syn && nb == 2 && tm == q;
                         if (fix0 || fix1) {
@@ -2712,8 +2351,7 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair2_n(const Repair2Args
                             for (int b = 0; b < 8; ++b)
                                 y[b][0] = fix1 ? f1[b][0] : f0[b][0];
                         } else {
-                            const u32 ib = __builtin_amdgcn_readfirstlane(
-                                (a.bbrick[tm >> 2] >> ((tm & 3u) * 8u)) & 0xFFu);
+                            const u32 ib = __builtin_amdgcn_readfirstlane(packed_byte(a.bbrick, tm));
                             const uint8_t *in = a.frag[ib];
 #pragma unroll
                             for (int b = 0; b < 8; ++b)
@@ -2732,8 +2370,7 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair2_n(const Repair2Args
                 /* the chunk this pass ends on: a check row's, or position d's */
                 const u32 pos = d ? q : p;
                 const u32 ob = __builtin_amdgcn_readfirstlane(
-                    solve ? (a.bbrick[pos >> 2] >> ((pos & 3u) * 8u)) & 0xFFu
-                          : (a.cbrick[row >> 2] >> ((row & 3u) * 8u)) & 0xFFu);
+                    solve ? packed_byte(a.bbrick, pos) : packed_byte(a.cbrick, row));
                 uint8_t *chunk = a.frag[ob] + off;
                 if (syn || solve) {
                     if (live) {

@@ -3164,20 +3164,6 @@ locate_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
     return rc;
 }
 
-static int32_t
-ecm_locate_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                const void *const *frags, uint32_t *loc, uint64_t *nbad)
-{
-    return locate_host(list, nstripes, avail_mask, frags, loc, nbad, 0);
-}
-
-static int32_t
-ecm_locate2_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                 const void *const *frags, uint32_t *loc, uint64_t *nbad)
-{
-    return locate_host(list, nstripes, avail_mask, frags, loc, nbad, 1);
-}
-
 /* Both device calls: `two` = ec_method_locate2_device. */
 static int32_t
 locate_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
@@ -3221,20 +3207,6 @@ locate_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripe
     if (two)
         return ecd_locate2(device, stream, &d, s.check, s.cb, s.bb, ratio, ratio1, pinv, loc);
     return ecd_locate(device, stream, &d, s.check, s.cb, s.bb, ratio, loc);
-}
-
-static int32_t
-ecm_locate_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
-                       uintptr_t avail_mask, const void *const *frags, uint32_t *loc)
-{
-    return locate_device(list, device, stream, nstripes, avail_mask, frags, loc, 0);
-}
-
-static int32_t
-ecm_locate2_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
-                        uintptr_t avail_mask, const void *const *frags, uint32_t *loc)
-{
-    return locate_device(list, device, stream, nstripes, avail_mask, frags, loc, 1);
 }
 
 /* ------------------------------------------- a read that checks and corrects */
@@ -3324,22 +3296,6 @@ decode_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_m
     return 0;
 }
 
-static int32_t
-ecm_decode_checked_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                        const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
-                        uint64_t *nmany)
-{
-    return decode_checked_host(list, nstripes, avail_mask, frags, out, loc, nbad, nmany, 0);
-}
-
-static int32_t
-ecm_decode_checked2_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                         const void *const *frags, void *out, uint32_t *loc, uint64_t *nbad,
-                         uint64_t *nmany)
-{
-    return decode_checked_host(list, nstripes, avail_mask, frags, out, loc, nbad, nmany, 1);
-}
-
 /* Both device calls: `two` = ec_method_decode_checked2_device. */
 static int32_t
 decode_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
@@ -3398,22 +3354,6 @@ decode_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t
                                    pat + d.k, ginv, out, loc);
     return ecd_decode_checked(device, stream, &d, s.check, s.cb, s.bb, ratio, pat + d.k, ginv, out,
                               loc);
-}
-
-static int32_t
-ecm_decode_checked_device_impl(ec_matrix_list_t *list, int device, void *stream,
-                               uint64_t nstripes, uintptr_t avail_mask,
-                               const void *const *frags, void *out, uint32_t *loc)
-{
-    return decode_checked_device(list, device, stream, nstripes, avail_mask, frags, out, loc, 0);
-}
-
-static int32_t
-ecm_decode_checked2_device_impl(ec_matrix_list_t *list, int device, void *stream,
-                                uint64_t nstripes, uintptr_t avail_mask,
-                                const void *const *frags, void *out, uint32_t *loc)
-{
-    return decode_checked_device(list, device, stream, nstripes, avail_mask, frags, out, loc, 1);
 }
 
 /* ------------------------------------------- repairing the named chunks */
@@ -3610,22 +3550,6 @@ repair_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
     return 0;
 }
 
-static int32_t
-ecm_repair_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                void *const *frags, const uint32_t *loc, uint64_t *nrepaired,
-                uint64_t *nskipped)
-{
-    return repair_host(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped, 0);
-}
-
-static int32_t
-ecm_repair2_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
-                 void *const *frags, const uint32_t *loc, uint64_t *nrepaired,
-                 uint64_t *nskipped)
-{
-    return repair_host(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped, 1);
-}
-
 /* Weak like ecd_repair: without the symbol ec_method_repair2_device is
  * -ENODEV. */
 extern __typeof__(ecd_repair2) ecd_repair2 __attribute__((weak));
@@ -3685,20 +3609,6 @@ repair_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripe
     }
     return ecd_repair2(device, stream, d.k, nstripes, frags, (uint32_t)avail_mask, ls.nr, G, ginv,
                        pinv, loc);
-}
-
-static int32_t
-ecm_repair_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
-                       uintptr_t avail_mask, void *const *frags, const uint32_t *loc)
-{
-    return repair_device(list, device, stream, nstripes, avail_mask, frags, loc, 0);
-}
-
-static int32_t
-ecm_repair2_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
-                        uintptr_t avail_mask, void *const *frags, const uint32_t *loc)
-{
-    return repair_device(list, device, stream, nstripes, avail_mask, frags, loc, 1);
 }
 
 /* ------------------------------------------------- partial-stripe writes */
@@ -4079,7 +3989,7 @@ ec_method_locate(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_locate", seq,
-                   ecm_locate_impl(list, nstripes, avail_mask, frags, loc, nbad));
+                   locate_host(list, nstripes, avail_mask, frags, loc, nbad, 0));
 }
 
 int32_t
@@ -4088,8 +3998,7 @@ ec_method_locate_device(ec_matrix_list_t *list, int device, void *stream, uint64
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_locate_device", seq,
-                   ecm_locate_device_impl(list, device, stream, nstripes, avail_mask, frags,
-                                          loc));
+                   locate_device(list, device, stream, nstripes, avail_mask, frags, loc, 0));
 }
 
 int32_t
@@ -4099,8 +4008,8 @@ ec_method_decode_checked(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t av
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_decode_checked", seq,
-                   ecm_decode_checked_impl(list, nstripes, avail_mask, frags, out, loc, nbad,
-                                           nmany));
+                   decode_checked_host(list, nstripes, avail_mask, frags, out, loc, nbad, nmany,
+                                       0));
 }
 
 int32_t
@@ -4110,8 +4019,8 @@ ec_method_decode_checked_device(ec_matrix_list_t *list, int device, void *stream
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_decode_checked_device", seq,
-                   ecm_decode_checked_device_impl(list, device, stream, nstripes, avail_mask,
-                                                  frags, out, loc));
+                   decode_checked_device(list, device, stream, nstripes, avail_mask, frags, out,
+                                         loc, 0));
 }
 
 int32_t
@@ -4121,8 +4030,8 @@ ec_method_decode_checked2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t a
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_decode_checked2", seq,
-                   ecm_decode_checked2_impl(list, nstripes, avail_mask, frags, out, loc, nbad,
-                                            nmany));
+                   decode_checked_host(list, nstripes, avail_mask, frags, out, loc, nbad, nmany,
+                                       1));
 }
 
 int32_t
@@ -4132,8 +4041,8 @@ ec_method_decode_checked2_device(ec_matrix_list_t *list, int device, void *strea
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_decode_checked2_device", seq,
-                   ecm_decode_checked2_device_impl(list, device, stream, nstripes, avail_mask,
-                                                   frags, out, loc));
+                   decode_checked_device(list, device, stream, nstripes, avail_mask, frags, out,
+                                         loc, 1));
 }
 
 int32_t
@@ -4142,7 +4051,7 @@ ec_method_locate2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mas
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_locate2", seq,
-                   ecm_locate2_impl(list, nstripes, avail_mask, frags, loc, nbad));
+                   locate_host(list, nstripes, avail_mask, frags, loc, nbad, 1));
 }
 
 int32_t
@@ -4151,8 +4060,7 @@ ec_method_locate2_device(ec_matrix_list_t *list, int device, void *stream, uint6
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_locate2_device", seq,
-                   ecm_locate2_device_impl(list, device, stream, nstripes, avail_mask, frags,
-                                           loc));
+                   locate_device(list, device, stream, nstripes, avail_mask, frags, loc, 1));
 }
 
 int32_t
@@ -4162,7 +4070,8 @@ ec_method_repair(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_repair", seq,
-                   ecm_repair_impl(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped));
+                   repair_host(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped,
+                               0));
 }
 
 int32_t
@@ -4171,8 +4080,7 @@ ec_method_repair_device(ec_matrix_list_t *list, int device, void *stream, uint64
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_repair_device", seq,
-                   ecm_repair_device_impl(list, device, stream, nstripes, avail_mask, frags,
-                                          loc));
+                   repair_device(list, device, stream, nstripes, avail_mask, frags, loc, 0));
 }
 
 int32_t
@@ -4182,7 +4090,8 @@ ec_method_repair2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mas
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_repair2", seq,
-                   ecm_repair2_impl(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped));
+                   repair_host(list, nstripes, avail_mask, frags, loc, nrepaired, nskipped,
+                               1));
 }
 
 int32_t
@@ -4191,8 +4100,7 @@ ec_method_repair2_device(ec_matrix_list_t *list, int device, void *stream, uint6
 {
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_repair2_device", seq,
-                   ecm_repair2_device_impl(list, device, stream, nstripes, avail_mask, frags,
-                                           loc));
+                   repair_device(list, device, stream, nstripes, avail_mask, frags, loc, 1));
 }
 
 int32_t

@@ -19,7 +19,9 @@ EC_MI355X_TILE_PERM and EC_HELPER_SPIN_US from the product: the XCD tile
 order is now a compile-time choice of the >= 4 GiB 16+4 encoder, covered by
 test_gpu_fullsize.py's 4 GiB slices of the 8 GiB job.)  Each runs here in its own process through the C ABI, bit-exact against the
 oracle on device-resident encode, full / partial decode (ragged tiles
-included) and mixed decode.
+included) and mixed decode, and runs the five scrub tile kernels (verify,
+locate, locate2, decode_checked, decode_checked2) on damaged fragments: no
+other test launches their non-temporal instantiations.
 """
 import os
 import subprocess
@@ -32,7 +34,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SCRIPT = r"""
-import itertools, sys
+import errno, itertools, sys
 sys.path.insert(0, "oracle")
 import numpy as np, torch
 import glusterfs_amd as g
@@ -65,6 +67,66 @@ for k, n in ((4, 6), (8, 12), (16, 20)):
                 L.decode_batch(nst, m, rows, [dfr[r - 1] for r in rows], out)
                 exp = O.decode(k, rows, [frags[r - 1] for r in rows])
                 assert np.array_equal(out.cpu().numpy(), exp), ("dec", k, n, nst, hex(m))
+        # the scrub family on 13 stripes (three full tiles and a ragged one),
+        # so that every knob, the non-temporal staging of EC_MI355X_LDSNT=1
+        # included, runs its five tile kernels.  Expected values by the MDS
+        # rule on oracle-encoded fragments: a damaged check chunk is named
+        # alone, a damaged basis chunk fails every check row, one or two
+        # damaged chunks are named and the reads return the data around them.
+        sn, two = 13, n - k >= 4
+        sdata = rb(512 * k * sn)
+        sfr = [f.copy() for f in O.encode(k, n, sdata)]
+        sfr[1][1 * 512 + 37] ^= 0x10                    # basis brick 1, stripe 1
+        sfr[k][6 * 512 + 300] ^= 0x01                   # check brick k, stripe 6
+        if two:                                         # a pair in the ragged tile
+            sfr[k - 1][12 * 512 + 5] ^= 0x80
+            sfr[k + 1][12 * 512 + 411] ^= 0x04
+        sd = [dev(f) for f in sfr]
+        MANY = g.ec_method.EC_MI355X_LOCATE_MANY
+        bmask, s_all, a1 = (1 << k) - 1, (1 << n) - 1, (1 << (k + 2)) - 1
+        cmask = s_all & ~bmask
+        want_bad, want1 = np.zeros(sn, np.uint32), np.zeros(sn, np.uint32)
+        want_bad[1], want_bad[6] = cmask, 1 << k
+        want1[1], want1[6] = 1 << 1, 1 << k
+        want2 = want1.copy()
+        if two:
+            want_bad[12], want1[12], want2[12] = cmask, MANY, 1 << (k - 1) | 1 << (k + 1)
+        def words():
+            return torch.full((sn,), -1, dtype=torch.int32, device="cuda")
+        def chunks():
+            return torch.full((512 * k * sn,), 0xA5, dtype=torch.uint8, device="cuda")
+        def u32(t):
+            return t.cpu().numpy().view(np.uint32)
+        bad, loc1, locd1, loc2, locd2 = words(), words(), words(), words(), words()
+        out1, out2 = chunks(), chunks()
+        fr1 = sd[:k + 2] + [None] * (n - k - 2)
+        torch.cuda.synchronize()
+        L.verify_device(0, None, sn, bmask, sd[:k], cmask, sd[k:], bad)
+        L.locate_device(0, None, sn, a1, fr1, loc1)
+        L.decode_checked_device(0, None, sn, a1, fr1, out1, locd1)
+        if two:
+            L.locate2_device(0, None, sn, s_all, sd, loc2)
+            L.decode_checked2_device(0, None, sn, s_all, sd, out2, locd2)
+        else:                                           # 4+2 has no k + 4 bricks
+            for call in (lambda: L.locate2_device(0, None, sn, s_all, sd, loc2),
+                         lambda: L.decode_checked2_device(0, None, sn, s_all, sd, out2, locd2)):
+                try:
+                    call()
+                except OSError as e:
+                    assert e.errno == errno.EINVAL, ("scrub 4+2", e)
+                else:
+                    raise AssertionError("locate2 / decode_checked2 on 4+2 did not fail")
+        g.sync_device(0)
+        assert np.array_equal(u32(bad), want_bad), ("verify", k, u32(bad))
+        assert np.array_equal(u32(loc1), want1), ("locate", k, u32(loc1))
+        assert np.array_equal(u32(locd1), want1), ("decode_checked loc", k, u32(locd1))
+        named = want1 != MANY                           # MANY promises no correction
+        assert np.array_equal(out1.cpu().numpy().reshape(sn, -1)[named],
+                              sdata.reshape(sn, -1)[named]), ("decode_checked out", k)
+        if two:
+            assert np.array_equal(u32(loc2), want2), ("locate2", k, u32(loc2))
+            assert np.array_equal(u32(locd2), want2), ("decode_checked2 loc", k, u32(locd2))
+            assert np.array_equal(out2.cpu().numpy(), sdata), ("decode_checked2 out", k)
         group, ng = 16, 12
         nst = group * ng
         frags = [rb(512 * nst) for _ in range(n)]
