@@ -94,6 +94,18 @@ int ecd_decode_checked(int device, void *stream, const ecd_combine_desc_t *d,
                        const void *const *check, const uint8_t *check_brick,
                        const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *inv,
                        const uint8_t *ginv, void *out, uint32_t *loc);
+/* A heal that checks its sources (ec_method_heal_checked_device): the
+ * arguments of ecd_locate with basis_brick ascending, then the m = ntargets
+ * rows heal[j * k + p] of the heal matrix of the targets from the k inputs
+ * (row j gives the chunk of target j), ginv[p] = 1 / G[0][p], and the m target
+ * fragments out[j] (device memory, nstripes * 512 bytes each, any byte
+ * alignment).  loc[t] is ecd_locate's.  Chunk t of out[j] gets row j applied
+ * to stripe t's k inputs, after the one input loc[t] names, if any, has been
+ * corrected to agree with the others. */
+int ecd_heal_checked(int device, void *stream, const ecd_combine_desc_t *d,
+                     const void *const *check, const uint8_t *check_brick,
+                     const uint8_t *basis_brick, const uint8_t *ratio, uint32_t ntargets,
+                     const uint8_t *heal, const uint8_t *ginv, void *const *out, uint32_t *loc);
 /* Locating up to two damaged bricks (ec_method_locate2_device): the
  * arguments of ecd_locate with d->rows >= 4, then ratio1[(r - 2) * k + p] =
  * G[r][p] / G[1][p] for the rows after the second, and for every pair of

@@ -1655,6 +1655,17 @@ int ecd_decode_checked(int device, void *stream, const ecd_combine_desc_t *d,
     });
 }
 
+int ecd_heal_checked(int device, void *stream, const ecd_combine_desc_t *d,
+                     const void *const *check, const uint8_t *check_brick,
+                     const uint8_t *basis_brick, const uint8_t *ratio, uint32_t ntargets,
+                     const uint8_t *heal, const uint8_t *ginv, void *const *out, uint32_t *loc)
+{
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_heal_checked(s, d, check, check_brick, basis_brick, ratio, ntargets, heal,
+                                 ginv, out, loc);
+    });
+}
+
 int ecd_locate2(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc)

@@ -30,6 +30,11 @@ int ecdk_decode_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *
                         const uint8_t *check_brick, const uint8_t *basis_brick,
                         const uint8_t *ratio, const uint8_t *inv, const uint8_t *ginv, void *out,
                         uint32_t *loc);
+/* the checked and corrected heal of ecd_heal_checked (ec_heal_checked_n) */
+int ecdk_heal_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                      const uint8_t *check_brick, const uint8_t *basis_brick,
+                      const uint8_t *ratio, uint32_t ntargets, const uint8_t *heal,
+                      const uint8_t *ginv, void *const *out, uint32_t *loc);
 /* the one or two damaged bricks per stripe of ecd_locate2 (ec_locate2_n) */
 int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                  const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,

@@ -14,7 +14,7 @@
  *            8-stripe ec_combine, 16 waves (two blocks fill a CU's 32 wave
  *            slots); both stage by LDS-DMA into a plane-major tile and
  *            multiply by a jump into the searched XOR programs
- *   scrub    five kernels on one narrow tile, the check fragments staged
+ *   scrub    six kernels on one narrow tile, the check fragments staged
  *            beside the basis, put together from phases that are each
  *            written once (ec_kernels_impl.h) and launched by one launcher
  *            (launch_scrub_tile):
@@ -29,6 +29,8 @@
  *   checked2 the same read around up to two chunks: ec_decode_checked2_n,
  *   decode   phases 1 to 3, at most four products XORed into the named basis
  *            chunks in LDS, one dense decode
+ *   checked  a heal that checks its sources: ec_heal_checked_n, the checked
+ *   heal     decode with the targets' heal matrix for inv(B), a row per target
  *   repair   the chunks locate named: ec_repair_n, a ballot scan of loc[]
  *            and up to four dirty stripes of one brick per wave, no LDS
  *   repair2  the one or two chunks locate2 named: ec_repair2_n, the same
@@ -899,7 +901,7 @@ struct ScrubCfg {
     static constexpr int K = K_, NW = NW_, LA = LA_;
 };
 
-/* The launch of a four-stripe scrub tile kernel, for all five of them.
+/* The launch of a four-stripe scrub tile kernel, for all six of them.
  * kernel(ScrubCfg<K, NW, LA>{}) gives the instantiation to run on the packed
  * arguments a; k, rows and nstripes are the geometry in a, align the OR of
  * its input addresses, nf the kernel's words per stripe, and a failed launch
@@ -1081,6 +1083,51 @@ int ecdk_decode_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *
                              [](auto c) {
         using C = decltype(c);
         return &ec_decode_checked_n<C::K, C::NW, C::LA>;
+    });
+}
+
+/* ------------------------------------------- a heal that checks its sources */
+
+/* As ecdk_locate, then ntargets: the m targets; heal: m x k bytes, the heal
+ * matrix of the targets from the basis (row j gives the chunk of target j);
+ * ginv: k bytes, 1 / coefficient of row 0; out: the m target fragments,
+ * nstripes * 512 device bytes each at any alignment.  Every table travels in
+ * the kernel arguments: nothing is uploaded. */
+int ecdk_heal_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                      const uint8_t *check_brick, const uint8_t *basis_brick,
+                      const uint8_t *ratio, uint32_t ntargets, const uint8_t *heal,
+                      const uint8_t *ginv, void *const *out, uint32_t *loc)
+{
+    static_assert(sizeof(HealCheckedArgs) <= 2048, "the tables must fit the kernel arguments");
+    HealCheckedArgs a;
+    uintptr_t o = 0;
+    if (!heal || !ginv || !out || ntargets == 0)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    if (int rc = pack_locate(d, check, check_brick, basis_brick, ratio, loc, a.l, &o))
+        return rc;
+    const u32 k = a.l.k, kw = a.l.kw;
+    /* the inputs and the targets are different bricks of at most 31 */
+    if (k + a.l.rows + ntargets >= ECD_MAX_ROWS || kw * ntargets > kLocateWords)
+        return -EINVAL;
+    a.m = ntargets;
+    for (u32 j = 0; j < ntargets; ++j) {
+        if (!out[j])
+            return -EINVAL;
+        a.out[j] = static_cast<uint8_t *>(out[j]);
+        for (u32 p = 0; p < k; ++p)
+            a.heal[j * kw + (p >> 2)] |= (u32)heal[j * k + p] << ((p & 3u) * 8u);
+    }
+    for (u32 p = 0; p < k; ++p) {
+        if (ginv[p] == 0)
+            return -EINVAL;
+        a.bmask |= 1u << basis_brick[p];
+        a.ginv[p >> 2] |= (u32)ginv[p] << ((p & 3u) * 8u);
+    }
+    return launch_scrub_tile(s, a, k, a.l.rows, a.l.nstripes, o, 2, "launch_heal_checked",
+                             [](auto c) {
+        using C = decltype(c);
+        return &ec_heal_checked_n<C::K, C::NW, C::LA>;
     });
 }
 

@@ -1518,6 +1518,21 @@ struct DecodeCheckedArgs {
     u32 ginv[ECD_MAX_K / 4];
 };
 
+/* Kernel arguments of ec_heal_checked_n: LocateArgs, then the m target
+ * fragments (chunk t of target j at out[j] + t * 512, any byte alignment), B
+ * as a brick mask, T = the heal matrix of the targets from B laid out like the
+ * coefficients (row j at word j * kw) and the k bytes 1 / G[0][p].  The a
+ * inputs and the m targets are different bricks of at most 31, so m * kw <=
+ * (29 - k) * ceil(k / 4), at most 64 words (k = 13): kLocateWords.  1,384
+ * bytes in all. */
+struct HealCheckedArgs {
+    LocateArgs l;
+    uint8_t *out[ECD_MAX_ROWS];
+    u32 bmask, m;
+    u32 heal[kLocateWords];
+    u32 ginv[ECD_MAX_K / 4];
+};
+
 constexpr u32 kLocate2Pairs = ECD_MAX_K * (ECD_MAX_K - 1) / 2;   /* C(16, 2) */
 
 /* Kernel arguments of ec_locate2_n: LocateArgs, then what the pairs need.
@@ -1551,7 +1566,7 @@ struct DecodeChecked2Args {
 
 /* ------------------------------------------ scrub: the phases, once each */
 
-/* The five tile kernels below share the narrow combine's shape: T = 4 stripes
+/* The six tile kernels below share the narrow combine's shape: T = 4 stripes
  * per block, 16 lanes per chunk, one dword column of all 8 planes per lane,
  * with the check fragments staged beside the basis.  The tile is (k + rows) *
  * 2 KiB, input p's slot at p * 2 KiB and plane-major as stage_tile lays it,
@@ -1901,6 +1916,39 @@ __device__ __forceinline__ void scrub_pairs(const ScrubTile &t, const Locate2Arg
     }
 }
 
+/* The correction of a single basis chunk, after phase 2's barrier, for a
+ * stripe whose result word names basis position p: the error in p is e = s_0 /
+ * G[0][p] (s_0 = G[0][p] * e when p alone is wrong), and XORing e into p's LDS
+ * slot puts the basis chunks on the one codeword the other a - 1 chunks lie
+ * on.  The coefficient must be wave-uniform and p differs per stripe: the
+ * tile's four stripes go one per wave item, each on its own 16 lanes (stripe
+ * s on lanes 16 s .. 16 s + 15), around one multiply site.  A stripe's words
+ * are final, and a named basis brick is the one bit of the second while the
+ * first has two or more (0 for stripes past nstripes); c = 0 (nothing to
+ * correct) multiplies to zero.  MANY stripes, check-brick stripes and stripes
+ * past nstripes are left alone.  ginv: the k bytes 1 / G[0][p]; bmask: B as a
+ * brick mask. */
+template <int NW>
+__device__ __forceinline__ void scrub_correct(const ScrubTile &t, u32 k, u32 bmask,
+                                              const u32 *ginv)
+{
+    const uint8_t *s0 = t.col + k * kScrubSlot;
+    for (u32 s = t.wave; s < kScrubT; s += NW) {
+        const u32 f = __builtin_amdgcn_readfirstlane(t.flags[s]);
+        const u32 bb = __builtin_amdgcn_readfirstlane(t.flags[kScrubT + s]);
+        const bool fix = (f & (f - 1u)) != 0 && bb != 0;
+        const u32 p = fix ? (u32)__builtin_popcount(bmask & (bb - 1u)) : 0u;
+        const u32 c = __builtin_amdgcn_readfirstlane(fix ? packed_byte(ginv, p) : 0u);
+        if (c == 0)
+            continue;
+        u32 acc[8][1] = {}, y[8][1];
+        read_column(s0, y);
+        ecgf::mul_xor_jt<1>(c, acc, y);
+        if (t.cs == s)
+            xor_column(t.col + p * kScrubSlot, acc);
+    }
+}
+
 /* The decode of the tile's (corrected) basis slots: the k output rows are
  * spread over the waves like the check rows of phase 1; row j is the sum of
  * inv(B)[j][p] * x_p over the basis slots and leaves by dword stores, 64
@@ -1918,7 +1966,25 @@ __device__ __forceinline__ void scrub_decode(const ScrubTile &t, const u32 *inv,
     }
 }
 
-/* ---------------------------------------------- scrub: the five tile kernels */
+/* The heal of the tile's (corrected) basis slots: the m target rows are
+ * spread over the waves like the check rows of phase 1; row j is the sum of
+ * T[j][p] * x_p over the basis slots -- only those are read -- and leaves by
+ * dword stores, 64 contiguous bytes per plane and stripe (chunk t of target j
+ * at out[j] + t * 512). */
+template <int K, int NW>
+__device__ __forceinline__ void scrub_heal(const ScrubTile &t, const u32 *heal, u32 k, u32 kw,
+                                           u32 m, uint8_t *const *out)
+{
+    const uint64_t o = (t.t0 + t.cs) * (uint64_t)ECD_CHUNK + t.cc * 4u;
+    for (u32 j = t.wave; j < m; j += NW) {
+        u32 acc[8][1];
+        row_product<K>(heal, j, kw, k, t.col, acc);
+        if (t.live)
+            store_chunk<1, true>(out[j] + o, acc);
+    }
+}
+
+/* ---------------------------------------------- scrub: the six tile kernels */
 
 /* ec_method_verify_device: do the stored fragments of `rows` bricks agree
  * with what the k basis fragments imply?  Phase 1 alone, with one word per
@@ -1990,17 +2056,10 @@ __global__ __launch_bounds__(NW * 64) void ec_locate2_n(const Locate2Args a)
 
 /* ec_method_decode_checked_device: decode the k lowest bricks and, in the
  * same pass, check them against the others and correct a single bad chunk:
- * ec_locate_n's phases, a correction in LDS, the dense decode.  A clean tile
- * skips phase 2 and the correction.
- *
- * The correction, for a stripe whose result word names basis position p: the
- * error in p is e = s_0 / G[0][p] (s_0 = G[0][p] * e when p alone is wrong),
- * and XORing e into p's LDS slot puts the basis chunks on the one codeword
- * the other a - 1 chunks lie on, so that one dense decode with inv(B) gives
- * what inv(B_i) would give from the undamaged chunks.  The coefficient must
- * be wave-uniform and p differs per stripe: the tile's four stripes go one
- * per wave item, each on its own 16 lanes, around one multiply site.  MANY
- * stripes, check-brick stripes and stripes past nstripes are left alone. */
+ * ec_locate_n's phases, a correction in LDS (scrub_correct), the dense
+ * decode.  A clean tile skips phase 2 and the correction.  After the
+ * correction one dense decode with inv(B) gives what inv(B_i) would give from
+ * the undamaged chunks. */
 template <int K, int NW, int LA = kLdsDmaDefault>
 __global__ __launch_bounds__(NW * 64) void ec_decode_checked_n(const DecodeCheckedArgs a)
 {
@@ -2014,28 +2073,39 @@ __global__ __launch_bounds__(NW * 64) void ec_decode_checked_n(const DecodeCheck
     if (scrub_dirty(t)) {
         scrub_single<NW>(t, a.l);
         __syncthreads();
-        /* stripe s of the tile, on lanes 16 s .. 16 s + 15 of one wave: its
-         * words are final, and a named basis brick is the one bit of the
-         * second while the first has two or more (0 for stripes past
-         * nstripes).  c = 0 (nothing to correct) multiplies to zero. */
-        const uint8_t *s0 = t.col + k * kScrubSlot;
-        for (u32 s = t.wave; s < kScrubT; s += NW) {
-            const u32 f = __builtin_amdgcn_readfirstlane(t.flags[s]);
-            const u32 bb = __builtin_amdgcn_readfirstlane(t.flags[kScrubT + s]);
-            const bool fix = (f & (f - 1u)) != 0 && bb != 0;
-            const u32 p = fix ? (u32)__builtin_popcount(a.bmask & (bb - 1u)) : 0u;
-            const u32 c = __builtin_amdgcn_readfirstlane(fix ? packed_byte(a.ginv, p) : 0u);
-            if (c == 0)
-                continue;
-            u32 acc[8][1] = {}, y[8][1];
-            read_column(s0, y);
-            ecgf::mul_xor_jt<1>(c, acc, y);
-            if (t.cs == s)
-                xor_column(t.col + p * kScrubSlot, acc);
-        }
+        scrub_correct<NW>(t, k, a.bmask, a.ginv);
         __syncthreads();
     }
     scrub_decode<K, NW>(t, a.inv, k, a.l.kw, a.out);
+    scrub_store_loc<2>(t, a.l);
+}
+
+/* ec_method_heal_checked_device: regenerate the fragments of the target
+ * bricks from the k lowest bricks at hand and, in the same pass, check those
+ * against the others and correct a single bad chunk: ec_decode_checked_n with
+ * the heal matrix T = E_target * inv(B) in the place of inv(B) and one output
+ * per target.  T does not depend on the stripe: after the correction the
+ * basis chunks of a stripe that names basis brick i lie on the codeword of
+ * the other a - 1 chunks, and T applied to them is what the heal matrix of
+ * B_i gives from the undamaged ones.  A clean tile skips phase 2 and the
+ * correction; MANY stripes are healed from B as stored. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_heal_checked_n(const HealCheckedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 k = a.l.k;
+    ScrubTile t = scrub_stage<2, NW, LA>(lds, a.l);
+    __syncthreads();
+    scrub_place(t, lds, a.l.nstripes);
+    scrub_syndromes<K, NW, true>(t, a.l.coef, a.l.cbrick, k, a.l.kw, a.l.rows);
+    __syncthreads();
+    if (scrub_dirty(t)) {
+        scrub_single<NW>(t, a.l);
+        __syncthreads();
+        scrub_correct<NW>(t, k, a.bmask, a.ginv);
+        __syncthreads();
+    }
+    scrub_heal<K, NW>(t, a.heal, k, a.l.kw, a.m, a.out);
     scrub_store_loc<2>(t, a.l);
 }
 

@@ -3356,6 +3356,157 @@ decode_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t
                               loc);
 }
 
+/* ------------------------------------------- a heal that checks its sources */
+
+/* Weak like ecd_locate: without the symbol ec_method_heal_checked_device is
+ * -ENODEV. */
+extern __typeof__(ecd_heal_checked) ecd_heal_checked __attribute__((weak));
+
+/* What both entry points check beside locate_args: the targets are bricks of
+ * the volume outside avail_mask, each with a buffer.  *nt gets their number. */
+static int
+heal_checked_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags,
+                  uintptr_t target_mask, void *const *out, const uint32_t *loc,
+                  ecm_locate_sets_t *s, uint32_t *nt)
+{
+    uint32_t j;
+    int rc;
+
+    rc = locate_args(list, avail_mask, frags, loc, s);
+    if (rc)
+        return rc;
+    if (!out || target_mask == 0 || (target_mask >> list->rows) != 0 ||
+        (target_mask & avail_mask) != 0)
+        return -EINVAL;
+    *nt = popcount_mask(target_mask);
+    for (j = 0; j < *nt; j++)
+        if (!out[j])
+            return -EINVAL;
+    return 0;
+}
+
+/* The host call.  The stripes are healed in runs that share a mask, as
+ * decode_checked_host decodes them; loc[] is ec_method_locate's. */
+static int32_t
+heal_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                  const void *const *frags, uintptr_t target_mask, void *const *out,
+                  uint32_t *loc, uint64_t *nbad, uint64_t *nmany)
+{
+    ecm_locate_sets_t s;
+    ecd_combine_desc_t d;
+    uint64_t t, t1, bad = 0, many = 0;
+    uintptr_t mask, cur = 0;
+    uint32_t rows[ECM_MAX_K], nt = 0, n, b, p, j;
+    int rc;
+
+    rc = heal_checked_args(list, avail_mask, frags, target_mask, out, loc, &s, &nt);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    /* host entry point: device buffers go to _device (locate_host looks at
+     * the fragments and loc before it writes) */
+    if (!bufs_on((const void *const *)out, nt, -1))
+        return -EINVAL;
+    rc = locate_host(list, nstripes, avail_mask, frags, loc, &bad, 0);
+    if (rc)
+        return rc;
+    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+    d.k = list->columns;
+    d.rows = nt;
+    d.npatterns = 1;
+    d.pat_bytes = d.k + nt * d.k;
+    d.in_stride = EC_METHOD_CHUNK_SIZE;
+    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    for (t = 0; t < nstripes; t = t1) {
+        mask = checked_mask(&s, loc[t]);
+        for (t1 = t; t1 < nstripes && checked_mask(&s, loc[t1]) == mask; t1++)
+            many += loc[t1] == EC_MI355X_LOCATE_MANY;
+        if (mask != cur) {
+            rows_from_mask(mask, rows);
+            if (!mask_rows_ok(list, mask, rows))
+                return -EINVAL;
+            rc = heal_pattern(list, mask, rows, target_mask, d.pat, &n);
+            if (rc)
+                return rc;
+            if (n != nt)
+                return -EINVAL;
+            cur = mask;
+        }
+        d.nstripes = t1 - t;
+        /* heal_pattern's input p is the p-th brick of the mask */
+        for (b = 0, p = 0; b < list->rows; b++)
+            if ((mask >> b) & 1)
+                d.in_base[p++] = (const uint8_t *)frags[b] + t * EC_METHOD_CHUNK_SIZE;
+        for (j = 0; j < nt; j++)
+            d.out_base[j] = (uint8_t *)out[j] + t * EC_METHOD_CHUNK_SIZE;
+        rc = ecc_combine(CTX(list)->isa, &d);
+        if (rc)
+            return rc;
+    }
+    if (nbad)
+        *nbad = bad;
+    if (nmany)
+        *nmany = many;
+    return 0;
+}
+
+/* The device call: locate's tables, T = the heal matrix of the targets from
+ * B, and 1 / G[0][p] for the correction. */
+static int32_t
+heal_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                    uintptr_t avail_mask, const void *const *frags, uintptr_t target_mask,
+                    void *const *out, uint32_t *loc)
+{
+    ecm_locate_sets_t s;
+    ecd_combine_desc_t d;
+    uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ginv[ECM_MAX_K];
+    uint8_t pat[ECM_MAX_K + ECM_MAX_N * ECM_MAX_K];
+    uint32_t nt = 0, n, p, q;
+    int rc;
+
+    rc = heal_checked_args(list, avail_mask, frags, target_mask, out, loc, &s, &nt);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    /* device entry point: every buffer lives on `device` */
+    if (device < 0)
+        return -EINVAL;
+    for (p = 0; p < list->columns; p++)
+        if (ecd_ptr_device(s.in[p]) != device)
+            return -EINVAL;
+    for (p = 0; p < s.nr; p++)
+        if (ecd_ptr_device(s.check[p]) != device)
+            return -EINVAL;
+    for (p = 0; p < nt; p++)
+        if (ecd_ptr_device(out[p]) != device)
+            return -EINVAL;
+    if (ecd_ptr_device(loc) != device)
+        return -EINVAL;
+    if (!ecd_heal_checked)
+        return -ENODEV;
+    rc = locate_tables(list, &s, &d, ratio);
+    if (rc == 0)
+        rc = heal_pattern(list, s.bmask, s.rows, target_mask, pat, &n);
+    if (rc)
+        return rc;
+    if (n != nt)
+        return -EINVAL;
+    /* 1 / G[0][p]: the error of basis position p from the first syndrome */
+    for (p = 0; p < d.k; p++) {
+        q = ec_method_gf_div(1, d.pat[d.k + p]);
+        if (q == 0 || q >= EC_GF_SIZE)
+            return -EINVAL;
+        ginv[p] = (uint8_t)q;
+    }
+    d.nstripes = nstripes;
+    for (p = 0; p < d.k; p++)
+        d.in_base[p] = s.in[p];
+    return ecd_heal_checked(device, stream, &d, s.check, s.cb, s.bb, ratio, nt, pat + d.k, ginv,
+                            out, loc);
+}
+
 /* ------------------------------------------- repairing the named chunks */
 
 /* Weak like ecd_locate: without the symbol ec_method_repair_device is
@@ -4043,6 +4194,29 @@ ec_method_decode_checked2_device(ec_matrix_list_t *list, int device, void *strea
     return ecm_ret("ec_method_decode_checked2_device", seq,
                    decode_checked_device(list, device, stream, nstripes, avail_mask, frags, out,
                                          loc, 1));
+}
+
+int32_t
+ec_method_heal_checked(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                       const void *const *frags, uintptr_t target_mask, void *const *out,
+                       uint32_t *loc, uint64_t *nbad, uint64_t *nmany)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_checked", seq,
+                   heal_checked_host(list, nstripes, avail_mask, frags, target_mask, out, loc,
+                                     nbad, nmany));
+}
+
+int32_t
+ec_method_heal_checked_device(ec_matrix_list_t *list, int device, void *stream,
+                              uint64_t nstripes, uintptr_t avail_mask,
+                              const void *const *frags, uintptr_t target_mask,
+                              void *const *out, uint32_t *loc)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_checked_device", seq,
+                   heal_checked_device(list, device, stream, nstripes, avail_mask, frags,
+                                       target_mask, out, loc));
 }
 
 int32_t

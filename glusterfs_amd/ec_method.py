@@ -59,6 +59,7 @@ EXPORTS = (
     "ec_method_repair2", "ec_method_repair2_device",
     "ec_method_decode_checked", "ec_method_decode_checked_device",
     "ec_method_decode_checked2", "ec_method_decode_checked2_device",
+    "ec_method_heal_checked", "ec_method_heal_checked_device",
 )
 
 
@@ -174,6 +175,9 @@ def _load():
         "ec_method_decode_checked2": (i32, [P, u64, up, vp, vp, vp, ctypes.POINTER(u64),
                                             ctypes.POINTER(u64)]),
         "ec_method_decode_checked2_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp, vp]),
+        "ec_method_heal_checked": (i32, [P, u64, up, vp, up, vp, vp, ctypes.POINTER(u64),
+                                         ctypes.POINTER(u64)]),
+        "ec_method_heal_checked_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
         "ec_method_repair": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64),
                                    ctypes.POINTER(u64)]),
         "ec_method_repair_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
@@ -582,6 +586,21 @@ class ECMatrixList:
                "ec_method_decode_checked")
         return nbad.value, nmany.value
 
+    def heal_checked(self, nstripes, avail_mask, frags, target_mask, out, loc):
+        """ec_method_heal_checked: a heal that checks its sources.  `frags`
+        and `loc` as for locate; `out[j]` (nstripes * 512 bytes) gets the
+        fragment of the j-th brick of target_mask, regenerated from the k
+        lowest bricks of avail_mask, around the one brick `loc` names for a
+        stripe, if any.  Returns (nbad, nmany): the stripes with a non-zero
+        entry, and those of them that are EC_MI355X_LOCATE_MANY (to be
+        treated as -EIO)."""
+        nbad, nmany = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib.ec_method_heal_checked(ctypes.byref(self._list), nstripes, avail_mask,
+                                          _ptr_array(frags), target_mask, _ptr_array(out),
+                                          addr(loc), ctypes.byref(nbad), ctypes.byref(nmany)),
+               "ec_method_heal_checked")
+        return nbad.value, nmany.value
+
     def locate2(self, nstripes, avail_mask, frags, loc):
         """ec_method_locate2: which one or two bricks' chunks are wrong?  As
         locate, with k + 4 bricks in avail_mask; `loc` gets 0, the bits of the
@@ -682,6 +701,14 @@ class ECMatrixList:
         return _check(lib.ec_method_decode_checked_device(
             ctypes.byref(self._list), device, stream, nstripes, avail_mask, _ptr_array(frags),
             addr(out), addr(loc)), "ec_method_decode_checked_device")
+
+    def heal_checked_device(self, device, stream, nstripes, avail_mask, frags, target_mask, out,
+                            loc):
+        """ec_method_heal_checked_device: the same on device buffers (every
+        `out[j]` and `loc` too), queued on `stream`; nothing is counted."""
+        return _check(lib.ec_method_heal_checked_device(
+            ctypes.byref(self._list), device, stream, nstripes, avail_mask, _ptr_array(frags),
+            target_mask, _ptr_array(out), addr(loc)), "ec_method_heal_checked_device")
 
     def locate2_device(self, device, stream, nstripes, avail_mask, frags, loc):
         """ec_method_locate2_device: the same on device buffers (`loc` too),

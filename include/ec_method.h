@@ -295,6 +295,67 @@ int32_t ec_method_decode_checked_device(ec_matrix_list_t *list, int device, void
                                         uint64_t nstripes, uintptr_t avail_mask,
                                         const void *const *frags, void *out, uint32_t *loc);
 
+/* A heal that checks its sources: ec_method_heal and ec_method_locate in one
+ * pass over the fragments.  ec_method_heal takes exactly k source fragments
+ * and trusts them, so one silently damaged chunk in a source comes back as a
+ * wrong chunk in every healed fragment with return code 0, and is then
+ * written to a new brick; this call reads the a >= k + 2 fragments at hand,
+ * names the bad brick per stripe and heals around it.  frags, avail_mask,
+ * loc, nbad and nmany as for ec_method_decode_checked; target_mask and out as
+ * for ec_method_heal: out[j] (nstripes*512 bytes) is the fragment of the j-th
+ * set bit of target_mask, and the device variant takes each out[j] at any byte
+ * alignment (loc wants 4).
+ *
+ * Let B be the k lowest bricks of avail_mask and B_i the k lowest bricks of
+ * avail_mask other than i.  loc[t] is exactly what ec_method_locate gives on
+ * the same arguments, every loc[0..nstripes) written, and chunk t of every
+ * out[j] is, from the stored chunks, what ec_method_heal gives for that stripe
+ * with the same target_mask and
+ *   loc[t] == 0                      mask B (the chunks are consistent: any k
+ *                                    give the same);
+ *   loc[t] == 1u << i                mask B_i.  For a check brick B_i = B and
+ *                                    the bad chunk changes nothing; for a
+ *                                    basis brick the damaged chunk is not
+ *                                    used;
+ *   loc[t] == EC_MI355X_LOCATE_MANY  mask B as stored: defined bytes, but the
+ *                                    caller must treat the stripe as -EIO.
+ * So wherever at most one chunk of a stripe is damaged, every out[j] chunk is
+ * the chunk the original data encodes to.  The a - k == 2 caveat of
+ * ec_method_locate carries over: two damaged chunks can imitate one, and the
+ * targets are then what the code implies.  Nothing in frags is written, nothing
+ * past nstripes*512 of any out[j], and only the out[j] of target_mask.
+ *
+ * The device variant can be followed on one stream, with no host
+ * synchronisation, by ec_method_repair_device on the same loc and then
+ * ec_method_locate_device: afterwards the sources are clean, the targets are
+ * right and the second locate is all zero.
+ *
+ * -EINVAL: everything ec_method_locate rejects; an empty target_mask, one
+ * with a bit at or above n, or one that overlaps avail_mask; a NULL out or a
+ * NULL out[j]; host and device buffers mixed, or given to the wrong entry
+ * point (the device variant wants every out[j] on `device` too).  A target
+ * beside k + 2 available bricks takes n - k >= 3, so every call on a 2+1 or a
+ * 4+2 volume is -EINVAL.  nstripes == 0 returns 0 after these checks and
+ * writes nothing.
+ *
+ * Like ec_method_decode_checked, the host variant runs on the calling
+ * thread's CPU engine whatever the volume's engine is and leaves
+ * ec_method_stats_t, the router and the run-time compiler alone; the device
+ * variant is asynchronous on `stream` with no host synchronisation (the heal
+ * matrix of the targets from B and every other table travel in the kernel
+ * arguments, nothing is uploaded), reads a and writes m = |target_mask| chunks
+ * per stripe, pre-zeroes nothing, uses no global atomics, writes each loc[t]
+ * by one plain store and counts nothing (-ENODEV where the device layer lacks
+ * it). */
+int32_t ec_method_heal_checked(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                               const void *const *frags, uintptr_t target_mask,
+                               void *const *out, uint32_t *loc, uint64_t *nbad,
+                               uint64_t *nmany);
+int32_t ec_method_heal_checked_device(ec_matrix_list_t *list, int device, void *stream,
+                                      uint64_t nstripes, uintptr_t avail_mask,
+                                      const void *const *frags, uintptr_t target_mask,
+                                      void *const *out, uint32_t *loc);
+
 /* Locating up to two damaged bricks.  Arguments, buffer rules, asynchrony
  * and error codes are ec_method_locate's, except that avail_mask must name
  * a >= k + 4 bricks: fewer bits are -EINVAL (so every call on a 2+1 or 4+2
