@@ -19,9 +19,11 @@ EC_MI355X_TILE_PERM and EC_HELPER_SPIN_US from the product: the XCD tile
 order is now a compile-time choice of the >= 4 GiB 16+4 encoder, covered by
 test_gpu_fullsize.py's 4 GiB slices of the 8 GiB job.)  Each runs here in its own process through the C ABI, bit-exact against the
 oracle on device-resident encode, full / partial decode (ragged tiles
-included) and mixed decode, and runs the five scrub tile kernels (verify,
-locate, locate2, decode_checked, decode_checked2) on damaged fragments: no
-other test launches their non-temporal instantiations.
+included) and mixed decode, and runs the six scrub tile kernels (verify,
+locate, locate2, decode_checked, decode_checked2, heal_checked) on damaged
+fragments, so that EC_MI355X_LDSNT=1 launches their non-temporal
+instantiations at every K (tests/test_gpu_scrub_sweep.py launches the 4-wave
+ones).
 """
 import os
 import subprocess
@@ -69,13 +71,16 @@ for k, n in ((4, 6), (8, 12), (16, 20)):
                 assert np.array_equal(out.cpu().numpy(), exp), ("dec", k, n, nst, hex(m))
         # the scrub family on 13 stripes (three full tiles and a ragged one),
         # so that every knob, the non-temporal staging of EC_MI355X_LDSNT=1
-        # included, runs its five tile kernels.  Expected values by the MDS
+        # included, runs its six tile kernels.  Expected values by the MDS
         # rule on oracle-encoded fragments: a damaged check chunk is named
         # alone, a damaged basis chunk fails every check row, one or two
-        # damaged chunks are named and the reads return the data around them.
+        # damaged chunks are named and the reads return the data around them,
+        # and the checked heal of the last brick from the lowest k + 2 gives
+        # its clean fragment wherever at most one chunk is damaged.
         sn, two = 13, n - k >= 4
         sdata = rb(512 * k * sn)
         sfr = [f.copy() for f in O.encode(k, n, sdata)]
+        tclean = sfr[n - 1].copy()
         sfr[1][1 * 512 + 37] ^= 0x10                    # basis brick 1, stripe 1
         sfr[k][6 * 512 + 300] ^= 0x01                   # check brick k, stripe 6
         if two:                                         # a pair in the ragged tile
@@ -99,6 +104,8 @@ for k, n in ((4, 6), (8, 12), (16, 20)):
             return t.cpu().numpy().view(np.uint32)
         bad, loc1, locd1, loc2, locd2 = words(), words(), words(), words(), words()
         out1, out2 = chunks(), chunks()
+        loch = words()
+        outh = torch.full((512 * sn,), 0xA5, dtype=torch.uint8, device="cuda")
         fr1 = sd[:k + 2] + [None] * (n - k - 2)
         torch.cuda.synchronize()
         L.verify_device(0, None, sn, bmask, sd[:k], cmask, sd[k:], bad)
@@ -116,6 +123,15 @@ for k, n in ((4, 6), (8, 12), (16, 20)):
                     assert e.errno == errno.EINVAL, ("scrub 4+2", e)
                 else:
                     raise AssertionError("locate2 / decode_checked2 on 4+2 did not fail")
+        if n - k >= 3:
+            L.heal_checked_device(0, None, sn, a1, fr1, 1 << (n - 1), [outh], loch)
+        else:                                           # 4+2 has no brick beside k + 2
+            try:
+                L.heal_checked_device(0, None, sn, a1, fr1, 1 << (n - 1), [outh], loch)
+            except OSError as e:
+                assert e.errno == errno.EINVAL, ("scrub 4+2", e)
+            else:
+                raise AssertionError("heal_checked on 4+2 did not fail")
         g.sync_device(0)
         assert np.array_equal(u32(bad), want_bad), ("verify", k, u32(bad))
         assert np.array_equal(u32(loc1), want1), ("locate", k, u32(loc1))
@@ -127,6 +143,10 @@ for k, n in ((4, 6), (8, 12), (16, 20)):
             assert np.array_equal(u32(loc2), want2), ("locate2", k, u32(loc2))
             assert np.array_equal(u32(locd2), want2), ("decode_checked2 loc", k, u32(locd2))
             assert np.array_equal(out2.cpu().numpy(), sdata), ("decode_checked2 out", k)
+        if n - k >= 3:
+            assert np.array_equal(u32(loch), want1), ("heal_checked loc", k, u32(loch))
+            assert np.array_equal(outh.cpu().numpy().reshape(sn, -1)[named],
+                                  tclean.reshape(sn, -1)[named]), ("heal_checked out", k)
         group, ng = 16, 12
         nst = group * ng
         frags = [rb(512 * nst) for _ in range(n)]
@@ -176,6 +196,26 @@ for k, n in ((4, 6), (8, 12), (16, 20)):
                 a0, a1 = gi * grp * 512, min(nst, (gi + 1) * grp) * 512
                 exp = O.decode(k, rws, [frags[r - 1][a0:a1] for r in rws])
                 assert np.array_equal(out[a0 * k:a1 * k], exp), ("host mixed", k, n, nst, gi)
+# 4+2 has no brick to heal beside k + 2: a 4+3 volume runs the checked heal at
+# K = 4 (one damaged basis chunk, one damaged check chunk in the ragged tile)
+k, n, sn = 4, 7, 13
+sdata = rb(512 * k * sn)
+clean = O.encode(k, n, sdata)
+sfr = [f.copy() for f in clean]
+sfr[2][3 * 512 + 9] ^= 0x20
+sfr[5][12 * 512 + 500] ^= 0x02
+want = np.zeros(sn, np.uint32)
+want[3], want[12] = 1 << 2, 1 << 5
+loch = torch.full((sn,), -1, dtype=torch.int32, device="cuda")
+outh = torch.full((512 * sn,), 0xA5, dtype=torch.uint8, device="cuda")
+sd = [dev(f) for f in sfr[:6]] + [None]
+torch.cuda.synchronize()
+with g.ECMatrixList(k, n) as L:
+    L.heal_checked_device(0, None, sn, 0x3F, sd, 1 << 6, [outh], loch)
+    g.sync_device(0)
+got = loch.cpu().numpy().view(np.uint32)
+assert np.array_equal(got, want), ("heal_checked loc", k, got)
+assert np.array_equal(outh.cpu().numpy(), clean[6]), ("heal_checked out", k)
 assert g.ec_method.stats()["cpu_fallbacks"] == 0   # every host call ran on the GPU
 print("ok")
 """
