@@ -106,6 +106,21 @@ int ecd_heal_checked(int device, void *stream, const ecd_combine_desc_t *d,
                      const void *const *check, const uint8_t *check_brick,
                      const uint8_t *basis_brick, const uint8_t *ratio, uint32_t ntargets,
                      const uint8_t *heal, const uint8_t *ginv, void *const *out, uint32_t *loc);
+/* A read that only detects (ec_method_decode_verified_device): the arguments
+ * of ecd_verify with d->rows >= 1, then inv[j * k + p], the decode matrix of
+ * the k inputs.  bad[t] is ecd_verify's; out (as for ecd_decode_checked) gets
+ * the decode of stripe t's k inputs as stored. */
+int ecd_decode_verified(int device, void *stream, const ecd_combine_desc_t *d,
+                        const void *const *check, const uint8_t *check_brick,
+                        const uint8_t *inv, void *out, uint32_t *bad);
+/* A heal that only detects (ec_method_heal_verified_device): the arguments
+ * of ecd_verify, then the m = ntargets rows heal[j * k + p] of the heal matrix
+ * of the targets from the k inputs and the m target fragments out[j] (as for
+ * ecd_heal_checked).  bad[t] is ecd_verify's; chunk t of out[j] gets row j
+ * applied to stripe t's k inputs as stored. */
+int ecd_heal_verified(int device, void *stream, const ecd_combine_desc_t *d,
+                      const void *const *check, const uint8_t *check_brick, uint32_t ntargets,
+                      const uint8_t *heal, void *const *out, uint32_t *bad);
 /* Locating up to two damaged bricks (ec_method_locate2_device): the
  * arguments of ecd_locate with d->rows >= 4, then ratio1[(r - 2) * k + p] =
  * G[r][p] / G[1][p] for the rows after the second, and for every pair of

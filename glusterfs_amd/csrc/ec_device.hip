@@ -1666,6 +1666,24 @@ int ecd_heal_checked(int device, void *stream, const ecd_combine_desc_t *d,
     });
 }
 
+int ecd_decode_verified(int device, void *stream, const ecd_combine_desc_t *d,
+                        const void *const *check, const uint8_t *check_brick,
+                        const uint8_t *inv, void *out, uint32_t *bad)
+{
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_decode_verified(s, d, check, check_brick, inv, out, bad);
+    });
+}
+
+int ecd_heal_verified(int device, void *stream, const ecd_combine_desc_t *d,
+                      const void *const *check, const uint8_t *check_brick, uint32_t ntargets,
+                      const uint8_t *heal, void *const *out, uint32_t *bad)
+{
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_heal_verified(s, d, check, check_brick, ntargets, heal, out, bad);
+    });
+}
+
 int ecd_locate2(int device, void *stream, const ecd_combine_desc_t *d, const void *const *check,
                 const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,
                 const uint8_t *ratio1, const uint8_t *pair_inv, uint32_t *loc)

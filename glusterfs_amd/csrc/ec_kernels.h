@@ -35,6 +35,14 @@ int ecdk_heal_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *co
                       const uint8_t *check_brick, const uint8_t *basis_brick,
                       const uint8_t *ratio, uint32_t ntargets, const uint8_t *heal,
                       const uint8_t *ginv, void *const *out, uint32_t *loc);
+/* the decode that only detects of ecd_decode_verified (ec_decode_verified_n) */
+int ecdk_decode_verified(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                         const uint8_t *check_brick, const uint8_t *inv, void *out,
+                         uint32_t *bad);
+/* the heal that only detects of ecd_heal_verified (ec_heal_verified_n) */
+int ecdk_heal_verified(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                       const uint8_t *check_brick, uint32_t ntargets, const uint8_t *heal,
+                       void *const *out, uint32_t *bad);
 /* the one or two damaged bricks per stripe of ecd_locate2 (ec_locate2_n) */
 int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                  const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,

@@ -31,7 +31,10 @@
  *            chunks in LDS, one dense decode
  *   checked  a heal that checks its sources: ec_heal_checked_n, the checked
  *   heal     decode with the targets' heal matrix for inv(B), a row per target
- *   repair   the chunks locate named: ec_repair_n, a ballot scan of loc[]
+ *   verified a read and a heal that only detect, from k + 1 fragments:
+ *            ec_decode_verified_n and ec_heal_verified_n on the same tile,
+ *            the check rows and the output rows in one loop (scrub_verified)
+ *   repair  the chunks locate named: ec_repair_n, a ballot scan of loc[]
  *            and up to four dirty stripes of one brick per wave, no LDS
  *   repair2  the one or two chunks locate2 named: ec_repair2_n, the same
  *            scan, a pair rebuilt from the syndromes and locate2's tables
@@ -1128,6 +1131,115 @@ int ecdk_heal_checked(hipStream_t s, const ecd_combine_desc_t *d, const void *co
                              [](auto c) {
         using C = decltype(c);
         return &ec_heal_checked_n<C::K, C::NW, C::LA>;
+    });
+}
+
+/* ------------------------------------------- detect-only from k + 1 */
+
+/* VerifyArgs' fields of DecodeVerifiedArgs or HealVerifiedArgs from what
+ * ecdk_verify is given; *align gets the OR of the input addresses. */
+template <typename A>
+static int pack_verified(const ecd_combine_desc_t *d, const void *const *check,
+                         const uint8_t *check_brick, uint32_t *bad, A &a, uintptr_t *align)
+{
+    if (d->k == 0 || d->k > ECD_MAX_K || d->rows == 0 || d->k + d->rows >= ECD_MAX_ROWS ||
+        d->npatterns != 1 || d->pat_ext || d->group_pattern ||
+        d->pat_bytes < d->k + d->rows * d->k || d->in_stride != ECD_CHUNK || !check ||
+        !check_brick || !bad || ((uintptr_t)bad & 3u))
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    a.k = d->k;
+    a.kw = (d->k + 3) / 4;
+    a.rows = d->rows;
+    a.nstripes = d->nstripes;
+    a.bad = bad;
+    uintptr_t o = 0;
+    for (u32 p = 0; p < a.k; ++p) {
+        const uint8_t src = d->pat[p];
+        if (src >= ECD_MAX_ROWS || !d->in_base[src])
+            return -EINVAL;
+        a.in[p] = static_cast<const uint8_t *>(d->in_base[src]);
+        o |= (uintptr_t)a.in[p];
+    }
+    for (u32 r = 0; r < a.rows; ++r) {
+        if (!check[r] || check_brick[r] >= 31)
+            return -EINVAL;
+        a.in[a.k + r] = static_cast<const uint8_t *>(check[r]);
+        o |= (uintptr_t)check[r];
+        a.brick[r >> 2] |= (u32)check_brick[r] << ((r & 3u) * 8u);
+    }
+    *align = o;
+    return 0;
+}
+
+/* rows [r0, r0 + n) of a scrub coefficient table from n x k bytes */
+static void pack_rows(u32 *coef, u32 r0, u32 n, u32 k, u32 kw, const uint8_t *m)
+{
+    for (u32 r = 0; r < n; ++r)
+        for (u32 p = 0; p < k; ++p)
+            coef[(r0 + r) * kw + (p >> 2)] |= (u32)m[r * k + p] << ((p & 3u) * 8u);
+}
+
+/* As ecdk_verify, then inv: k x k bytes, the decode matrix of the basis (row
+ * j gives output chunk j); out: nstripes * k * 512 device bytes at any
+ * alignment.  Every table travels in the kernel arguments: nothing is
+ * uploaded. */
+int ecdk_decode_verified(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                         const uint8_t *check_brick, const uint8_t *inv, void *out,
+                         uint32_t *bad)
+{
+    static_assert(sizeof(DecodeVerifiedArgs) <= 2048, "the tables must fit the kernel arguments");
+    static_assert((ECD_MAX_ROWS - 1) * (ECD_MAX_K / 4) <= kMaxPatWords,
+                  "check rows and inv(B) share one table");
+    DecodeVerifiedArgs a;
+    uintptr_t o = 0;
+    if (!inv || !out)
+        return -EINVAL;
+    if (int rc = pack_verified(d, check, check_brick, bad, a, &o))
+        return rc;
+    /* a rows of kw words: at most 31 * 4 */
+    pack_rows(a.coef, 0, a.rows, a.k, a.kw, d->pat + a.k);
+    pack_rows(a.coef, a.rows, a.k, a.k, a.kw, inv);
+    a.out = static_cast<uint8_t *>(out);
+    return launch_scrub_tile(s, a, a.k, a.rows, a.nstripes, o, 1, "launch_decode_verified",
+                             [](auto c) {
+        using C = decltype(c);
+        return &ec_decode_verified_n<C::K, C::NW, C::LA>;
+    });
+}
+
+/* As ecdk_verify, then ntargets: the m targets; heal: m x k bytes, the heal
+ * matrix of the targets from the basis (row j gives the chunk of target j);
+ * out: the m target fragments, nstripes * 512 device bytes each at any
+ * alignment.  Every table travels in the kernel arguments: nothing is
+ * uploaded. */
+int ecdk_heal_verified(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                       const uint8_t *check_brick, uint32_t ntargets, const uint8_t *heal,
+                       void *const *out, uint32_t *bad)
+{
+    static_assert(sizeof(HealVerifiedArgs) <= 2048, "the tables must fit the kernel arguments");
+    HealVerifiedArgs a;
+    uintptr_t o = 0;
+    if (!heal || !out || ntargets == 0)
+        return -EINVAL;
+    if (int rc = pack_verified(d, check, check_brick, bad, a, &o))
+        return rc;
+    /* the inputs and the targets are different bricks of at most 31, so the
+     * table has at most 31 - k rows: 72 words at k = 13 */
+    if (a.k + a.rows + ntargets >= ECD_MAX_ROWS)
+        return -EINVAL;
+    a.m = ntargets;
+    pack_rows(a.coef, 0, a.rows, a.k, a.kw, d->pat + a.k);
+    pack_rows(a.coef, a.rows, ntargets, a.k, a.kw, heal);
+    for (u32 j = 0; j < ntargets; ++j) {
+        if (!out[j])
+            return -EINVAL;
+        a.out[j] = static_cast<uint8_t *>(out[j]);
+    }
+    return launch_scrub_tile(s, a, a.k, a.rows, a.nstripes, o, 1, "launch_heal_verified",
+                             [](auto c) {
+        using C = decltype(c);
+        return &ec_heal_verified_n<C::K, C::NW, C::LA>;
     });
 }
 

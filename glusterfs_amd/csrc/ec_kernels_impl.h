@@ -1533,6 +1533,37 @@ struct HealCheckedArgs {
     u32 ginv[ECD_MAX_K / 4];
 };
 
+/* Kernel arguments of ec_decode_verified_n: VerifyArgs' fields -- in the same
+ * places, so scrub_stage reads either -- then the decoded output (stripe t at
+ * out + t * k * 512, any byte alignment).  coef holds one table: the check
+ * rows, then the k rows of inv(B) from row `rows` on, kw words a row.  (a - k)
+ * + k rows of ceil(k / 4) words are at most 31 * 4 = 124 words. */
+struct DecodeVerifiedArgs {
+    const uint8_t *in[ECD_MAX_ROWS];
+    u32 *bad;
+    uint64_t nstripes;
+    u32 k, kw, rows, pad;
+    u32 brick[ECD_MAX_ROWS / 4];
+    u32 coef[kMaxPatWords];
+    uint8_t *out;
+};
+
+/* Kernel arguments of ec_heal_verified_n: VerifyArgs' fields, then the m
+ * target fragments (chunk t of target j at out[j] + t * 512, any byte
+ * alignment).  coef holds one table: the check rows, then the m rows of T =
+ * the heal matrix of the targets from B from row `rows` on.  The a inputs and
+ * the m targets are different bricks of at most 31, so there are at most 31 -
+ * k rows: (31 - k) * ceil(k / 4) <= 72 words (k = 13).  1,096 bytes in all. */
+struct HealVerifiedArgs {
+    const uint8_t *in[ECD_MAX_ROWS];
+    u32 *bad;
+    uint64_t nstripes;
+    u32 k, kw, rows, m;
+    u32 brick[ECD_MAX_ROWS / 4];
+    u32 coef[kMaxPatWords];
+    uint8_t *out[ECD_MAX_ROWS];
+};
+
 constexpr u32 kLocate2Pairs = ECD_MAX_K * (ECD_MAX_K - 1) / 2;   /* C(16, 2) */
 
 /* Kernel arguments of ec_locate2_n: LocateArgs, then what the pairs need.
@@ -1566,8 +1597,9 @@ struct DecodeChecked2Args {
 
 /* ------------------------------------------ scrub: the phases, once each */
 
-/* The six tile kernels below share the narrow combine's shape: T = 4 stripes
- * per block, 16 lanes per chunk, one dword column of all 8 planes per lane,
+/* The tile kernels below (six, and the two detect-only ones after them) share
+ * the narrow combine's shape: T = 4 stripes per block, 16 lanes per chunk,
+ * one dword column of all 8 planes per lane,
  * with the check fragments staged beside the basis.  The tile is (k + rows) *
  * 2 KiB, input p's slot at p * 2 KiB and plane-major as stage_tile lays it,
  * then up to three u32 words per stripe:
@@ -2182,6 +2214,77 @@ __global__ __launch_bounds__(NW * 64) void ec_decode_checked2_n(const DecodeChec
     }
     scrub_decode<K, NW>(t, a.inv, k, l.kw, a.out);
     scrub_store_loc<3>(t, l);
+}
+
+/* ------------------------------- scrub: detect-only, two more tile kernels */
+
+/* The coding work of the two detect-only kernels, one loop around one
+ * multiply site: `items` rows of one coefficient table are spread over the
+ * waves, the `rows` check rows first and the output rows after them, and
+ * every one is a product with the basis slots alone -- no stored chunk is
+ * overwritten, so the rows do not depend on one another and need no barrier
+ * between them.  Which kind a row is is wave-uniform.  A check row is phase
+ * 1's (scrub_syndromes without KEEP): any bit in which the product differs
+ * from stored slot k + r is a mismatch, the 16 lanes of a stripe vote and one
+ * of them ORs the row's brick bit into flags[s].  An output row leaves like
+ * scrub_decode's and scrub_heal's, to dest(j), the lane's dword of plane 0 of
+ * output row j. */
+template <int K, int NW, typename Dest>
+__device__ __forceinline__ void scrub_verified(const ScrubTile &t, const u32 *coef,
+                                               const u32 *brick, u32 k, u32 kw, u32 rows,
+                                               u32 items, Dest dest)
+{
+    for (u32 r = t.wave; r < items; r += NW) {
+        u32 acc[8][1];
+        row_product<K>(coef, r, kw, k, t.col, acc);
+        if (r < rows) {
+            const u32 d = or_diff(0, t.col + (k + r) * kScrubSlot, acc);
+            const uint64_t vote = __ballot(t.live && d != 0);
+            const u32 bit = __builtin_amdgcn_readfirstlane(packed_byte(brick, r));
+            if (t.cc == 0 && ((vote >> (t.cs * 16u)) & 0xFFFFu) != 0)
+                atomicOr(&t.flags[t.cs], 1u << bit);
+        } else if (t.live) {
+            store_chunk<1, true>(dest(r - rows), acc);
+        }
+    }
+}
+
+/* ec_method_decode_verified_device: decode the k lowest bricks as stored and,
+ * in the same pass over the tile, check them against the others: bad[t] is
+ * ec_verify_n's word and nothing is corrected. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_decode_verified_n(const DecodeVerifiedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 k = a.k;
+    ScrubTile t = scrub_stage<1, NW, LA>(lds, a);
+    __syncthreads();
+    scrub_place(t, lds, a.nstripes);
+    uint8_t *o = a.out + (t.t0 + t.cs) * ((uint64_t)k * ECD_CHUNK) + t.cc * 4u;
+    scrub_verified<K, NW>(t, a.coef, a.brick, k, a.kw, a.rows, a.rows + k,
+                          [&](u32 j) { return o + j * ECD_CHUNK; });
+    __syncthreads();
+    if (t.tid < kScrubT && t.t0 + t.tid < a.nstripes)
+        a.bad[t.t0 + t.tid] = t.flags[t.tid];
+}
+
+/* ec_method_heal_verified_device: regenerate the fragments of the m target
+ * bricks from the k lowest bricks at hand as stored and, in the same pass,
+ * check those against the others: ec_decode_verified_n with the heal matrix T
+ * = E_target * inv(B) in the place of inv(B) and one output per target. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_heal_verified_n(const HealVerifiedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    ScrubTile t = scrub_stage<1, NW, LA>(lds, a);
+    __syncthreads();
+    scrub_place(t, lds, a.nstripes);
+    const uint64_t o = (t.t0 + t.cs) * (uint64_t)ECD_CHUNK + t.cc * 4u;
+    scrub_verified<K, NW>(t, a.coef, a.brick, a.k, a.kw, a.rows, a.rows + a.m,
+                          [&](u32 j) { return a.out[j] + o; });
+    __syncthreads();
+    if (t.tid < kScrubT && t.t0 + t.tid < a.nstripes)
+        a.bad[t.t0 + t.tid] = t.flags[t.tid];
 }
 
 /* ------------------------------------------- repairing the named chunks */

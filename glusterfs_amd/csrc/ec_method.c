@@ -2799,15 +2799,16 @@ typedef struct {
     const void *check[ECM_MAX_N];
 } ecm_locate_sets_t;
 
+/* `spare`: how many bricks beside the basis the call needs at least. */
 static int
-locate_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags,
-            const uint32_t *loc, ecm_locate_sets_t *s)
+avail_sets(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags,
+           const uint32_t *loc, uint32_t spare, ecm_locate_sets_t *s)
 {
     uint32_t i, nb = 0, nr = 0;
 
     if (!list || !CTX(list) || !frags || !loc || ((uintptr_t)loc & 3u))
         return -EINVAL;
-    if ((avail_mask >> list->rows) != 0 || popcount_mask(avail_mask) < list->columns + 2)
+    if ((avail_mask >> list->rows) != 0 || popcount_mask(avail_mask) < list->columns + spare)
         return -EINVAL;
     s->bmask = s->rmask = 0;
     for (i = 0; i < list->rows; i++) {
@@ -2828,6 +2829,13 @@ locate_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *fra
     s->nr = nr;
     rows_from_mask(s->bmask, s->rows);
     return mask_rows_ok(list, s->bmask, s->rows) ? 0 : -EINVAL;
+}
+
+static int
+locate_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags,
+            const uint32_t *loc, ecm_locate_sets_t *s)
+{
+    return avail_sets(list, avail_mask, frags, loc, 2, s);
 }
 
 /* The prediction matrix G (nr x k, in d->pat after its k source bytes) and
@@ -3505,6 +3513,165 @@ heal_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t n
         d.in_base[p] = s.in[p];
     return ecd_heal_checked(device, stream, &d, s.check, s.cb, s.bb, ratio, nt, pat + d.k, ginv,
                             out, loc);
+}
+
+/* ------------------------------------------- detect-only from k + 1 */
+
+/* Weak like ecd_heal_checked: without the symbols
+ * ec_method_decode_verified_device and ec_method_heal_verified_device are
+ * -ENODEV. */
+extern __typeof__(ecd_decode_verified) ecd_decode_verified __attribute__((weak));
+extern __typeof__(ecd_heal_verified) ecd_heal_verified __attribute__((weak));
+
+/* What the four entry points check: locate_args' rules with one brick beside
+ * the basis instead of two, and an output.  With `heal`, out is the list of
+ * target fragments and heal_checked_args' rules for target_mask hold; *nt
+ * gets the number of targets. */
+static int
+verified_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags, int heal,
+              uintptr_t target_mask, const void *out, const uint32_t *bad,
+              ecm_locate_sets_t *s, uint32_t *nt)
+{
+    void *const *outs = (void *const *)out;
+    uint32_t j;
+    int rc;
+
+    rc = avail_sets(list, avail_mask, frags, bad, 1, s);
+    if (rc)
+        return rc;
+    if (!out)
+        return -EINVAL;
+    *nt = 0;
+    if (!heal)
+        return 0;
+    if (target_mask == 0 || (target_mask >> list->rows) != 0 || (target_mask & avail_mask) != 0)
+        return -EINVAL;
+    *nt = popcount_mask(target_mask);
+    for (j = 0; j < *nt; j++)
+        if (!outs[j])
+            return -EINVAL;
+    return 0;
+}
+
+/* Both host calls.  The flags are ec_method_verify's with B and C; the
+ * output is one combine with the pattern of B, whatever the flags say. */
+static int32_t
+verified_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+              const void *const *frags, int heal, uintptr_t target_mask, void *out,
+              uint32_t *bad, uint64_t *nbad)
+{
+    void *const *outs = (void *const *)out;
+    ecm_locate_sets_t s;
+    ecd_combine_desc_t d;
+    uint32_t k, nt = 0, n = 0, b, j;
+    int rc;
+
+    rc = verified_args(list, avail_mask, frags, heal, target_mask, out, bad, &s, &nt);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    /* host entry point: device buffers go to _device (ecm_verify_impl looks
+     * at the fragments and bad before it writes) */
+    if (heal ? !bufs_on((const void *const *)outs, nt, -1) : ecd_ptr_device(out) >= 0)
+        return -EINVAL;
+    k = list->columns;
+    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+    if (heal) {
+        rc = heal_pattern(list, s.bmask, s.rows, target_mask, d.pat, &n);
+        if (rc == 0 && n != nt)
+            rc = -EINVAL;
+    } else {
+        rc = mask_pattern(list, s.bmask, d.pat);
+    }
+    if (rc)
+        return rc;
+    rc = ecm_verify_impl(list, nstripes, s.bmask, s.in, s.rmask, s.check, bad, nbad);
+    if (rc)
+        return rc;
+    d.k = k;
+    d.rows = heal ? nt : k;
+    d.nstripes = nstripes;
+    d.npatterns = 1;
+    d.pat_bytes = k + d.rows * k;
+    d.in_stride = EC_METHOD_CHUNK_SIZE;
+    d.out_stride = heal ? EC_METHOD_CHUNK_SIZE : (uint64_t)k * EC_METHOD_CHUNK_SIZE;
+    if (heal) {
+        /* heal_pattern's input p is the p-th brick of the mask */
+        for (b = 0; b < k; b++)
+            d.in_base[b] = s.in[b];
+        for (j = 0; j < nt; j++)
+            d.out_base[j] = outs[j];
+    } else {
+        /* mask_pattern's inputs are indexed by brick */
+        for (b = 0; b < list->rows; b++)
+            d.in_base[b] = (s.bmask >> b) & 1 ? frags[b] : NULL;
+        for (j = 0; j < k; j++)
+            d.out_base[j] = (uint8_t *)out + (size_t)j * EC_METHOD_CHUNK_SIZE;
+    }
+    return ecc_combine(CTX(list)->isa, &d);
+}
+
+/* Both device calls: verify's prediction rows of C from B, then inv(B) or T =
+ * the heal matrix of the targets from B. */
+static int32_t
+verified_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                uintptr_t avail_mask, const void *const *frags, int heal,
+                uintptr_t target_mask, void *out, uint32_t *bad)
+{
+    void *const *outs = (void *const *)out;
+    ecm_locate_sets_t s;
+    ecd_combine_desc_t d;
+    uint8_t pat[ECM_MAX_K + ECM_MAX_N * ECM_MAX_K];
+    uint32_t nt = 0, nc = 0, n = 0, p;
+    int rc;
+
+    rc = verified_args(list, avail_mask, frags, heal, target_mask, out, bad, &s, &nt);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    /* device entry point: every buffer lives on `device` */
+    if (device < 0)
+        return -EINVAL;
+    for (p = 0; p < list->columns; p++)
+        if (ecd_ptr_device(s.in[p]) != device)
+            return -EINVAL;
+    for (p = 0; p < s.nr; p++)
+        if (ecd_ptr_device(s.check[p]) != device)
+            return -EINVAL;
+    for (p = 0; p < nt; p++)
+        if (ecd_ptr_device(outs[p]) != device)
+            return -EINVAL;
+    if (ecd_ptr_device(bad) != device || (!heal && ecd_ptr_device(out) != device))
+        return -EINVAL;
+    if (heal ? !ecd_heal_verified : !ecd_decode_verified)
+        return -ENODEV;
+    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+    rc = heal_pattern(list, s.bmask, s.rows, s.rmask, d.pat, &nc);
+    if (rc == 0 && nc != s.nr)
+        rc = -EINVAL;
+    if (rc == 0 && heal) {
+        rc = heal_pattern(list, s.bmask, s.rows, target_mask, pat, &n);
+        if (rc == 0 && n != nt)
+            rc = -EINVAL;
+    } else if (rc == 0) {
+        rc = mask_pattern(list, s.bmask, pat);
+    }
+    if (rc)
+        return rc;
+    d.k = list->columns;
+    d.rows = nc;
+    d.nstripes = nstripes;
+    d.npatterns = 1;
+    d.pat_bytes = d.k + nc * d.k;
+    d.in_stride = EC_METHOD_CHUNK_SIZE;
+    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    for (p = 0; p < d.k; p++)
+        d.in_base[p] = s.in[p];
+    if (heal)
+        return ecd_heal_verified(device, stream, &d, s.check, s.cb, nt, pat + d.k, outs, bad);
+    return ecd_decode_verified(device, stream, &d, s.check, s.cb, pat + d.k, out, bad);
 }
 
 /* ------------------------------------------- repairing the named chunks */
@@ -4217,6 +4384,49 @@ ec_method_heal_checked_device(ec_matrix_list_t *list, int device, void *stream,
     return ecm_ret("ec_method_heal_checked_device", seq,
                    heal_checked_device(list, device, stream, nstripes, avail_mask, frags,
                                        target_mask, out, loc));
+}
+
+int32_t
+ec_method_decode_verified(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                          const void *const *frags, void *out, uint32_t *bad, uint64_t *nbad)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_decode_verified", seq,
+                   verified_host(list, nstripes, avail_mask, frags, 0, 0, out, bad, nbad));
+}
+
+int32_t
+ec_method_decode_verified_device(ec_matrix_list_t *list, int device, void *stream,
+                                 uint64_t nstripes, uintptr_t avail_mask,
+                                 const void *const *frags, void *out, uint32_t *bad)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_decode_verified_device", seq,
+                   verified_device(list, device, stream, nstripes, avail_mask, frags, 0, 0, out,
+                                   bad));
+}
+
+int32_t
+ec_method_heal_verified(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                        const void *const *frags, uintptr_t target_mask, void *const *out,
+                        uint32_t *bad, uint64_t *nbad)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_verified", seq,
+                   verified_host(list, nstripes, avail_mask, frags, 1, target_mask, (void *)out,
+                                 bad, nbad));
+}
+
+int32_t
+ec_method_heal_verified_device(ec_matrix_list_t *list, int device, void *stream,
+                               uint64_t nstripes, uintptr_t avail_mask,
+                               const void *const *frags, uintptr_t target_mask,
+                               void *const *out, uint32_t *bad)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_verified_device", seq,
+                   verified_device(list, device, stream, nstripes, avail_mask, frags, 1,
+                                   target_mask, (void *)out, bad));
 }
 
 int32_t

@@ -60,6 +60,8 @@ EXPORTS = (
     "ec_method_decode_checked", "ec_method_decode_checked_device",
     "ec_method_decode_checked2", "ec_method_decode_checked2_device",
     "ec_method_heal_checked", "ec_method_heal_checked_device",
+    "ec_method_decode_verified", "ec_method_decode_verified_device",
+    "ec_method_heal_verified", "ec_method_heal_verified_device",
 )
 
 
@@ -178,6 +180,10 @@ def _load():
         "ec_method_heal_checked": (i32, [P, u64, up, vp, up, vp, vp, ctypes.POINTER(u64),
                                          ctypes.POINTER(u64)]),
         "ec_method_heal_checked_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
+        "ec_method_decode_verified": (i32, [P, u64, up, vp, vp, vp, ctypes.POINTER(u64)]),
+        "ec_method_decode_verified_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp, vp]),
+        "ec_method_heal_verified": (i32, [P, u64, up, vp, up, vp, vp, ctypes.POINTER(u64)]),
+        "ec_method_heal_verified_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
         "ec_method_repair": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64),
                                    ctypes.POINTER(u64)]),
         "ec_method_repair_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
@@ -601,6 +607,31 @@ class ECMatrixList:
                "ec_method_heal_checked")
         return nbad.value, nmany.value
 
+    def decode_verified(self, nstripes, avail_mask, frags, out, bad):
+        """ec_method_decode_verified: a read that only detects.  `frags` as
+        for locate, with k + 1 bricks in avail_mask; `out` (nstripes * k * 512
+        bytes) gets the decode of the k lowest bricks of avail_mask as stored
+        and `bad` (uint32, one per stripe) verify's flags of the other bricks
+        against them.  Returns the number of stripes with a non-zero flag."""
+        nbad = ctypes.c_uint64(0)
+        _check(lib.ec_method_decode_verified(ctypes.byref(self._list), nstripes, avail_mask,
+                                             _ptr_array(frags), addr(out), addr(bad),
+                                             ctypes.byref(nbad)), "ec_method_decode_verified")
+        return nbad.value
+
+    def heal_verified(self, nstripes, avail_mask, frags, target_mask, out, bad):
+        """ec_method_heal_verified: a heal that only detects.  `frags` and
+        `bad` as for decode_verified; `out[j]` (nstripes * 512 bytes) gets the
+        fragment of the j-th brick of target_mask, regenerated from the k
+        lowest bricks of avail_mask as stored.  Returns the number of stripes
+        with a non-zero flag."""
+        nbad = ctypes.c_uint64(0)
+        _check(lib.ec_method_heal_verified(ctypes.byref(self._list), nstripes, avail_mask,
+                                           _ptr_array(frags), target_mask, _ptr_array(out),
+                                           addr(bad), ctypes.byref(nbad)),
+               "ec_method_heal_verified")
+        return nbad.value
+
     def locate2(self, nstripes, avail_mask, frags, loc):
         """ec_method_locate2: which one or two bricks' chunks are wrong?  As
         locate, with k + 4 bricks in avail_mask; `loc` gets 0, the bits of the
@@ -709,6 +740,21 @@ class ECMatrixList:
         return _check(lib.ec_method_heal_checked_device(
             ctypes.byref(self._list), device, stream, nstripes, avail_mask, _ptr_array(frags),
             target_mask, _ptr_array(out), addr(loc)), "ec_method_heal_checked_device")
+
+    def decode_verified_device(self, device, stream, nstripes, avail_mask, frags, out, bad):
+        """ec_method_decode_verified_device: the same on device buffers (`out`
+        and `bad` too), queued on `stream`; nothing is counted."""
+        return _check(lib.ec_method_decode_verified_device(
+            ctypes.byref(self._list), device, stream, nstripes, avail_mask, _ptr_array(frags),
+            addr(out), addr(bad)), "ec_method_decode_verified_device")
+
+    def heal_verified_device(self, device, stream, nstripes, avail_mask, frags, target_mask,
+                             out, bad):
+        """ec_method_heal_verified_device: the same on device buffers (every
+        `out[j]` and `bad` too), queued on `stream`; nothing is counted."""
+        return _check(lib.ec_method_heal_verified_device(
+            ctypes.byref(self._list), device, stream, nstripes, avail_mask, _ptr_array(frags),
+            target_mask, _ptr_array(out), addr(bad)), "ec_method_heal_verified_device")
 
     def locate2_device(self, device, stream, nstripes, avail_mask, frags, loc):
         """ec_method_locate2_device: the same on device buffers (`loc` too),

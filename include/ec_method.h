@@ -356,6 +356,74 @@ int32_t ec_method_heal_checked_device(ec_matrix_list_t *list, int device, void *
                                       const void *const *frags, uintptr_t target_mask,
                                       void *const *out, uint32_t *loc);
 
+/* A read and a heal that only detect, from k + 1 fragments.  The checked
+ * calls above want a >= k + 2 fragments, which leaves out every 2+1 volume, a
+ * 4+2 read with one brick down and the ordinary 4+2 heal (five sources, one
+ * target).  With a = k + 1 the code cannot name the bad brick, but it can say
+ * that a stripe is inconsistent: these calls are ec_method_decode (or
+ * ec_method_heal) and ec_method_verify in one pass over the fragments, so
+ * that a caller can answer -EIO instead of wrong bytes.  frags and avail_mask
+ * are ec_method_locate's, indexed by brick -- entries outside avail_mask are
+ * not read and may be NULL -- except that a >= k + 1 bricks are enough.
+ *
+ * Let B be the k lowest bricks of avail_mask and C the others (a - k >= 1).
+ *   bad[t]   exactly what ec_method_verify gives with mask = B and check_mask
+ *            = C on the same buffers: bit i is set when brick i is in C and
+ *            its stored chunk t differs from what the chunks of B imply.
+ *            Every bad[0..nstripes) is written, each by one plain store.
+ *            *nbad (host variants, may be NULL) = stripes with bad[t] != 0.
+ *   out      of decode_verified: nstripes*k*512 bytes, stripe t at out +
+ *            t*k*512, the layout of ec_method_decode_device's out (any byte
+ *            alignment on the device).  Stripe t is always ec_method_decode
+ *            with mask B as stored, byte for byte.
+ *   out[j]   of heal_verified: the fragment of the j-th set bit of
+ *            target_mask, chunk t at out[j] + t*512, as in ec_method_heal
+ *            (any byte alignment on the device).  It is always ec_method_heal
+ *            with mask B and the same target_mask, as stored.
+ * Nothing is corrected, so:
+ *   bad[t] == 0   the a chunks are mutually consistent and the output is
+ *                 right;
+ *   otherwise     with a == k + 1 the stripe cannot be trusted and is to be
+ *                 treated as -EIO.  With a >= k + 2 a single bit means that
+ *                 check brick alone is bad and the output is right; every
+ *                 bit of C set means a basis chunk is damaged (or several
+ *                 chunks are) and the output is wrong.  A caller that holds
+ *                 k + 2 fragments or more then runs ec_method_decode_checked
+ *                 or ec_method_heal_checked.
+ * Nothing in frags is written, nothing past out + nstripes*k*512, nothing
+ * past nstripes*512 of any out[j], and only the out[j] of target_mask.
+ *
+ * -EINVAL: a NULL list, frags, bad or out; bad not 4-byte aligned; a bit of
+ * avail_mask at or above n; fewer than k + 1 bits; a NULL frags[i] for a set
+ * bit; host and device buffers mixed, or given to the wrong entry point (the
+ * device variants want every buffer, bad and the outputs included, on
+ * `device`); for the heal also an empty target_mask, one with a bit at or
+ * above n, one that overlaps avail_mask, or a NULL out[j].  A target beside
+ * k + 1 sources takes n - k >= 2, so every heal_verified call on a 2+1 volume
+ * is -EINVAL.  nstripes == 0 returns 0 after these checks and writes nothing.
+ * One avail_mask per call.
+ *
+ * Like ec_method_verify, the host variants run on the calling thread's CPU
+ * engine whatever the volume's engine is and leave ec_method_stats_t, the
+ * router and the run-time compiler alone; the device variants are
+ * asynchronous on `stream` with no host synchronisation (every table travels
+ * in the kernel arguments, nothing is uploaded), read a and write k or m =
+ * |target_mask| chunks per stripe, pre-zero nothing, use no global atomics
+ * and count nothing (-ENODEV where the device layer lacks the call). */
+int32_t ec_method_decode_verified(ec_matrix_list_t *list, uint64_t nstripes,
+                                  uintptr_t avail_mask, const void *const *frags, void *out,
+                                  uint32_t *bad, uint64_t *nbad);
+int32_t ec_method_decode_verified_device(ec_matrix_list_t *list, int device, void *stream,
+                                         uint64_t nstripes, uintptr_t avail_mask,
+                                         const void *const *frags, void *out, uint32_t *bad);
+int32_t ec_method_heal_verified(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                                const void *const *frags, uintptr_t target_mask,
+                                void *const *out, uint32_t *bad, uint64_t *nbad);
+int32_t ec_method_heal_verified_device(ec_matrix_list_t *list, int device, void *stream,
+                                       uint64_t nstripes, uintptr_t avail_mask,
+                                       const void *const *frags, uintptr_t target_mask,
+                                       void *const *out, uint32_t *bad);
+
 /* Locating up to two damaged bricks.  Arguments, buffer rules, asynchrony
  * and error codes are ec_method_locate's, except that avail_mask must name
  * a >= k + 4 bricks: fewer bits are -EINVAL (so every call on a 2+1 or 4+2

@@ -1,0 +1,18 @@
+"""The host variants of the detect-only read and heal under ASan + UBSan: the
+host layer built around the device-layer stub, as tests/test_sanitizers.py
+builds it (the link is the same: the new device entries are weak references),
+driving tests/c/verified_check.c, a stand-alone program whose buffers have
+exactly the sizes the contract names.  CPU only; the build takes seconds."""
+import os
+import subprocess
+
+from test_sanitizers import build
+
+
+def test_verified_host_variants_under_asan_ubsan(tmp_path):
+    exe = build(tmp_path, ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                main="verified_check")
+    env = dict(os.environ, EC_MI355X_QUIET="1", ASAN_OPTIONS="detect_leaks=1")
+    env.pop("EC_GPU_ALWAYS", None)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "failures=0" in r.stdout, (r.stdout + r.stderr)[-4000:]
