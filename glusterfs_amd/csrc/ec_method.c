@@ -1677,6 +1677,32 @@ bufs_on(const void *const *b, uint32_t n, int dev)
     return 1;
 }
 
+/* The descriptor of a combine with one pattern: k inputs, `rows` outputs,
+ * the byte distance between two stripes on either side.  Only the fields
+ * before pat are cleared, so a pattern may be put into d->pat before or after
+ * this call; the pointers are the caller's.  A host loop that combines window
+ * by window or run by run passes nstripes = 0 and sets it each time. */
+static void
+desc_init(ecd_combine_desc_t *d, uint32_t k, uint32_t rows, uint64_t nstripes,
+          uint64_t in_stride, uint64_t out_stride)
+{
+    memset(d, 0, offsetof(ecd_combine_desc_t, pat));
+    d->k = k;
+    d->rows = rows;
+    d->nstripes = nstripes;
+    d->npatterns = 1;
+    d->pat_bytes = k + rows * k;
+    d->in_stride = in_stride;
+    d->out_stride = out_stride;
+}
+
+/* desc_init from fragments to fragments: chunk after chunk on both sides */
+static void
+desc_init_frags(ecd_combine_desc_t *d, uint32_t k, uint32_t rows, uint64_t nstripes)
+{
+    desc_init(d, k, rows, nstripes, EC_METHOD_CHUNK_SIZE, EC_METHOD_CHUNK_SIZE);
+}
+
 static uint32_t
 popcount_mask(uintptr_t m)
 {
@@ -2099,18 +2125,11 @@ cpu_encode_rows(const ecm_ctx_t *ctx, uint64_t s0, uint64_t s1, const void *in, 
     ecd_combine_desc_t d;
     uint32_t p;
 
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
-    d.k = ctx->k;
-    d.rows = m;
-    d.nstripes = s1 - s0;
-    d.in_stride = S;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    desc_init(&d, ctx->k, m, s1 - s0, S, EC_METHOD_CHUNK_SIZE);
     for (p = 0; p < ctx->k; p++)
         d.in_base[p] = (const uint8_t *)in + s0 * S + (uint64_t)p * EC_METHOD_CHUNK_SIZE;
     for (p = 0; p < m; p++)
         d.out_base[p] = (uint8_t *)outs[p] + s0 * EC_METHOD_CHUNK_SIZE;
-    d.npatterns = 1;
-    d.pat_bytes = ctx->k + m * ctx->k;
     d.pat_ext = pat;
     return ecc_combine(ctx->isa, &d);
 }
@@ -2210,18 +2229,12 @@ device_encode_rows(ecm_ctx_t *ctx, int dev, void *stream, uint64_t nstripes, con
     ecd_combine_desc_t d;
     uint32_t p;
 
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
-    d.k = ctx->k;
-    d.rows = m;
-    d.nstripes = nstripes;
-    d.in_stride = (uint64_t)ctx->k * EC_METHOD_CHUNK_SIZE;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    desc_init(&d, ctx->k, m, nstripes, (uint64_t)ctx->k * EC_METHOD_CHUNK_SIZE,
+              EC_METHOD_CHUNK_SIZE);
     for (p = 0; p < ctx->k; p++)
         d.in_base[p] = (const uint8_t *)in + (uint64_t)p * EC_METHOD_CHUNK_SIZE;
     for (p = 0; p < m; p++)
         d.out_base[p] = outs[p];
-    d.npatterns = 1;
-    d.pat_bytes = ctx->k + m * ctx->k;
     memcpy(d.pat, pat, d.pat_bytes);
     return ecd_combine(dev, stream, &d);
 }
@@ -2637,160 +2650,17 @@ ecm_heal_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask,
                        pat, NULL, 0);
 }
 
-/* ------------------------------------------- consistency check (scrub) */
+/* ------------------------------------------- steps the scrub calls share */
 
-/* A host-only build links a stand-in of the device layer that may lack the
- * check's device entry (tests/c/ecd_stub.c): the reference is weak, and
- * without the symbol ec_method_verify_device is -ENODEV. */
-extern __typeof__(ecd_verify) ecd_verify __attribute__((weak));
+/* The calls below (verify, locate, repair, the checked and the verified reads
+ * and heals) are made of these steps, each written here once.  Every host
+ * and device function keeps one order: its argument checks, the zero-stripes
+ * return, where the buffers live (-EINVAL), for a device call the weak ecd_*
+ * symbol (-ENODEV), and only then its tables. */
 
-#define ECM_VERIFY_STRIPES 32u /* stripes predicted per pass of the host check */
-
-/* Arguments both entry points share: the masks, the pointer arrays and the
- * alignment of bad[].  rows[] gets the bricks of mask, bricks[] / *nc those
- * of check_mask. */
-static int
-verify_args(ec_matrix_list_t *list, uintptr_t mask, const void *const *in, uintptr_t check_mask,
-            const void *const *check, const uint32_t *bad, uint32_t *rows, uint8_t *bricks,
-            uint32_t *nc)
-{
-    uint32_t i, c = 0;
-
-    if (!list || !CTX(list) || !in || !check || !bad || ((uintptr_t)bad & 3u))
-        return -EINVAL;
-    rows_from_mask(mask, rows);
-    if (!mask_rows_ok(list, mask, rows))
-        return -EINVAL;
-    if (check_mask == 0 || (check_mask >> list->rows) != 0 || (check_mask & mask) != 0)
-        return -EINVAL;
-    for (i = 0; i < list->rows; i++)
-        if ((check_mask >> i) & 1)
-            bricks[c++] = (uint8_t)i;
-    *nc = c;
-    return 0;
-}
-
-static int32_t
-ecm_verify_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask, const void *const *in,
-                uintptr_t check_mask, const void *const *check, uint32_t *bad, uint64_t *nbad)
-{
-    ecd_combine_desc_t d;
-    uint32_t rows[ECM_MAX_K], nc = 0, nt = 0, p, r, flag;
-    uint8_t bricks[ECM_MAX_N];
-    uint64_t s0, t, n, count = 0;
-    uint8_t *scratch;
-    int rc;
-
-    rc = verify_args(list, mask, in, check_mask, check, bad, rows, bricks, &nc);
-    if (rc)
-        return rc;
-    if (nstripes == 0)
-        return 0;
-    /* host entry point: device buffers go to _device */
-    for (p = 0; p < list->columns; p++)
-        if (!in[p] || ecd_ptr_device(in[p]) >= 0)
-            return -EINVAL;
-    for (r = 0; r < nc; r++)
-        if (!check[r] || ecd_ptr_device(check[r]) >= 0)
-            return -EINVAL;
-    if (ecd_ptr_device(bad) >= 0)
-        return -EINVAL;
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
-    rc = heal_pattern(list, mask, rows, check_mask, d.pat, &nt);
-    if (rc)
-        return rc;
-    /* the CPU engine predicts a few dozen stripes of the check bricks into
-     * scratch, then every chunk is compared with the stored one */
-    scratch = (uint8_t *)malloc((size_t)ECM_VERIFY_STRIPES * nt * EC_METHOD_CHUNK_SIZE);
-    if (!scratch)
-        return -ENOMEM;
-    d.k = list->columns;
-    d.rows = nt;
-    d.npatterns = 1;
-    d.pat_bytes = d.k + nt * d.k;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
-    for (r = 0; r < nt; r++)
-        d.out_base[r] = scratch + (size_t)r * ECM_VERIFY_STRIPES * EC_METHOD_CHUNK_SIZE;
-    for (s0 = 0; s0 < nstripes && rc == 0; s0 += n) {
-        n = nstripes - s0 < ECM_VERIFY_STRIPES ? nstripes - s0 : ECM_VERIFY_STRIPES;
-        d.nstripes = n;
-        for (p = 0; p < d.k; p++)
-            d.in_base[p] = (const uint8_t *)in[p] + s0 * EC_METHOD_CHUNK_SIZE;
-        rc = ecc_combine(CTX(list)->isa, &d);
-        if (rc)
-            break;
-        for (t = 0; t < n; t++) {
-            flag = 0;
-            for (r = 0; r < nt; r++)
-                if (memcmp((const uint8_t *)d.out_base[r] + t * EC_METHOD_CHUNK_SIZE,
-                           (const uint8_t *)check[r] + (s0 + t) * EC_METHOD_CHUNK_SIZE,
-                           EC_METHOD_CHUNK_SIZE) != 0)
-                    flag |= 1u << bricks[r];
-            bad[s0 + t] = flag;
-            count += flag != 0;
-        }
-    }
-    free(scratch);
-    if (rc == 0 && nbad)
-        *nbad = count;
-    return rc;
-}
-
-static int32_t
-ecm_verify_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
-                       uintptr_t mask, const void *const *in, uintptr_t check_mask,
-                       const void *const *check, uint32_t *bad)
-{
-    ecd_combine_desc_t d;
-    uint32_t rows[ECM_MAX_K], nc = 0, nt = 0, p, r;
-    uint8_t bricks[ECM_MAX_N];
-    int rc;
-
-    rc = verify_args(list, mask, in, check_mask, check, bad, rows, bricks, &nc);
-    if (rc)
-        return rc;
-    if (nstripes == 0)
-        return 0;
-    /* device entry point: every buffer lives on `device` */
-    if (device < 0)
-        return -EINVAL;
-    for (p = 0; p < list->columns; p++)
-        if (!in[p] || ecd_ptr_device(in[p]) != device)
-            return -EINVAL;
-    for (r = 0; r < nc; r++)
-        if (!check[r] || ecd_ptr_device(check[r]) != device)
-            return -EINVAL;
-    if (ecd_ptr_device(bad) != device)
-        return -EINVAL;
-    if (!ecd_verify)
-        return -ENODEV;
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
-    rc = heal_pattern(list, mask, rows, check_mask, d.pat, &nt);
-    if (rc)
-        return rc;
-    d.k = list->columns;
-    d.rows = nt;
-    d.nstripes = nstripes;
-    d.npatterns = 1;
-    d.pat_bytes = d.k + nt * d.k;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
-    for (p = 0; p < d.k; p++)
-        d.in_base[p] = in[p];
-    return ecd_verify(device, stream, &d, check, bricks, bad);
-}
-
-/* ------------------------------------------- locating the damaged brick */
-
-/* Weak like ecd_verify: without the symbol ec_method_locate_device is
- * -ENODEV. */
-extern __typeof__(ecd_locate) ecd_locate __attribute__((weak));
-
-/* What both entry points derive from avail_mask: the basis B (its k lowest
- * bricks; rows[] = their matrix rows, bb[] = their indices), the check set R
- * (the other nr = a - k >= 2 bricks, cb[]), and the pointer lists in that
- * order. */
+/* What the calls derive from avail_mask: the basis B (its k lowest bricks;
+ * rows[] = their matrix rows, bb[] = their indices), the check set R (the
+ * other nr = a - k bricks, cb[]), and the pointer lists in that order. */
 typedef struct {
     uintptr_t bmask, rmask;
     uint32_t rows[ECM_MAX_K], nr;
@@ -2799,7 +2669,9 @@ typedef struct {
     const void *check[ECM_MAX_N];
 } ecm_locate_sets_t;
 
-/* `spare`: how many bricks beside the basis the call needs at least. */
+/* The opening of every call that takes avail_mask: list, frags and the
+ * aligned flag words `loc`, a mask inside the volume with at least k + `spare`
+ * bricks, and a fragment for every brick of it. */
 static int
 avail_sets(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags,
            const uint32_t *loc, uint32_t spare, ecm_locate_sets_t *s)
@@ -2831,25 +2703,304 @@ avail_sets(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frag
     return mask_rows_ok(list, s->bmask, s->rows) ? 0 : -EINVAL;
 }
 
+/* The targets of a heal: bricks of the volume outside avail_mask, at least
+ * one, each with a buffer in out[].  *nt gets their number. */
 static int
-locate_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags,
-            const uint32_t *loc, ecm_locate_sets_t *s)
+heal_targets_ok(const ec_matrix_list_t *list, uintptr_t avail_mask, uintptr_t target_mask,
+                void *const *out, uint32_t *nt)
 {
-    return avail_sets(list, avail_mask, frags, loc, 2, s);
+    uint32_t j;
+
+    if (!out || target_mask == 0 || (target_mask >> list->rows) != 0 ||
+        (target_mask & avail_mask) != 0)
+        return 0;
+    *nt = popcount_mask(target_mask);
+    for (j = 0; j < *nt; j++)
+        if (!out[j])
+            return 0;
+    return 1;
 }
 
-/* The prediction matrix G (nr x k, in d->pat after its k source bytes) and
- * the ratios q[c][b] = G[c][b] / G[c0][b] of the rows after the first, (nr -
- * 1) x k.  The code is MDS, so no entry of G is zero. */
+/* Where the buffers of a call live: 1 when the inputs, the check fragments,
+ * the output fragments and the single buffers a and b are all on `dev` (-1:
+ * host memory).  A list of no entries and a NULL buffer pass (bufs_on), so a
+ * call names what it has: NULL entries were rejected before, except by
+ * verify, which looks itself.  ecd_ptr_device answers -1 or the index of a
+ * device, so "not on a device" and "on -1" are one test. */
 static int
-locate_tables(ec_matrix_list_t *list, const ecm_locate_sets_t *s, ecd_combine_desc_t *d,
-              uint8_t *ratio)
+scrub_bufs_on(int dev, const void *const *in, uint32_t nin, const void *const *check,
+              uint32_t ncheck, void *const *outs, uint32_t nouts, const void *a, const void *b)
+{
+    const void *single[2] = {a, b};
+
+    return bufs_on(in, nin, dev) && bufs_on(check, ncheck, dev) &&
+           bufs_on((const void *const *)outs, nouts, dev) && bufs_on(single, 2, dev);
+}
+
+/* host entry point: device buffers go to _device */
+static int
+scrub_on_host(const void *const *in, uint32_t nin, const void *const *check, uint32_t ncheck,
+              void *const *outs, uint32_t nouts, const void *a, const void *b)
+{
+    return scrub_bufs_on(-1, in, nin, check, ncheck, outs, nouts, a, b);
+}
+
+/* device entry point: every buffer lives on `device` */
+static int
+scrub_on_device(int device, const void *const *in, uint32_t nin, const void *const *check,
+                uint32_t ncheck, void *const *outs, uint32_t nouts, const void *a, const void *b)
+{
+    return device >= 0 && scrub_bufs_on(device, in, nin, check, ncheck, outs, nouts, a, b);
+}
+
+#define ECM_VERIFY_STRIPES 32u /* stripes predicted per window of the host check */
+
+/* What check_pass hands over for a stripe whose chunks differ: `diff` has bit
+ * r set when row r of the prediction differs from the stored chunk of
+ * check[r]; the predicted chunk of row r is at pred + r * pred_stride, the
+ * stored one at check[r] + t * 512.  *flag is the stripe's word of flags[]. */
+typedef int (*ecm_check_fn)(void *arg, uint64_t t, uint32_t diff, const uint8_t *pred,
+                            size_t pred_stride, uint32_t *flag);
+
+/* The host check pass.  d holds the pattern that predicts the d->rows check
+ * fragments from the d->k inputs.  The CPU engine predicts a window of a few
+ * dozen stripes into scratch, then every chunk is compared with the stored
+ * one: a clean stripe gets flags[t] = 0, any other goes to `differs`, whose
+ * error ends the pass.  *nbad (may be NULL) = stripes that differ, written on
+ * success only. */
+static int
+check_pass(int isa, ecd_combine_desc_t *d, uint64_t nstripes, const void *const *in,
+           const void *const *check, uint32_t *flags, uint64_t *nbad, ecm_check_fn differs,
+           void *arg)
+{
+    const size_t row = (size_t)ECM_VERIFY_STRIPES * EC_METHOD_CHUNK_SIZE;
+    uint64_t s0, t, n, count = 0;
+    uint32_t p, r, diff;
+    uint8_t *scratch;
+    int rc = 0;
+
+    scratch = (uint8_t *)malloc(row * d->rows);
+    if (!scratch)
+        return -ENOMEM;
+    for (r = 0; r < d->rows; r++)
+        d->out_base[r] = scratch + r * row;
+    for (s0 = 0; s0 < nstripes && rc == 0; s0 += n) {
+        n = nstripes - s0 < ECM_VERIFY_STRIPES ? nstripes - s0 : ECM_VERIFY_STRIPES;
+        d->nstripes = n;
+        for (p = 0; p < d->k; p++)
+            d->in_base[p] = (const uint8_t *)in[p] + s0 * EC_METHOD_CHUNK_SIZE;
+        rc = ecc_combine(isa, d);
+        for (t = 0; t < n && rc == 0; t++) {
+            diff = 0;
+            for (r = 0; r < d->rows; r++)
+                if (memcmp(scratch + r * row + t * EC_METHOD_CHUNK_SIZE,
+                           (const uint8_t *)check[r] + (s0 + t) * EC_METHOD_CHUNK_SIZE,
+                           EC_METHOD_CHUNK_SIZE) != 0)
+                    diff |= 1u << r;
+            flags[s0 + t] = 0;
+            if (diff) {
+                rc = differs(arg, s0 + t, diff, scratch + t * EC_METHOD_CHUNK_SIZE, row,
+                             &flags[s0 + t]);
+                count++;
+            }
+        }
+    }
+    free(scratch);
+    if (rc == 0 && nbad)
+        *nbad = count;
+    return rc;
+}
+
+/* The mask stripe t is decoded with: B, or B_S = B without the basis bricks
+ * loc[t] names and with as many of the lowest check bricks it does not name
+ * (for one basis brick i that is B_i: B without i and with c0).  MANY is bit
+ * 31 and no mask has a bit there. */
+static uintptr_t
+checked_mask(const ecm_locate_sets_t *s, uint32_t w)
+{
+    uintptr_t named = (uintptr_t)w & s->bmask, spare = s->rmask & ~(uintptr_t)w;
+    uintptr_t mask = s->bmask & ~named;
+
+    for (; named; named &= named - 1, spare &= spare - 1)
+        mask |= spare & (~spare + 1);
+    return mask;
+}
+
+/* A walk over loc[] in runs of stripes that share a decode mask: a run is one
+ * combine.  Start from all zero.  A run ends where the mask changes, so each
+ * one needs a pattern of its own: there is nothing to keep from the last. */
+typedef struct {
+    uint64_t t, t1;  /* the run: stripes [t, t1) */
+    uintptr_t mask;  /* checked_mask of each of them */
+    uint64_t many;   /* stripes with EC_MI355X_LOCATE_MANY so far */
+} ecm_mask_run_t;
+
+static int
+mask_run_next(ecm_mask_run_t *r, const ecm_locate_sets_t *s, const uint32_t *loc,
+              uint64_t nstripes)
+{
+    r->t = r->t1;
+    if (r->t >= nstripes)
+        return 0;
+    r->mask = checked_mask(s, loc[r->t]);
+    for (; r->t1 < nstripes && checked_mask(s, loc[r->t1]) == r->mask; r->t1++)
+        r->many += loc[r->t1] == EC_MI355X_LOCATE_MANY;
+    return 1;
+}
+
+/* dst[i] = 1 / src[i] for n coefficients of a prediction matrix.  The code
+ * is MDS, so none is zero: one that is, or is no field element, is -EINVAL. */
+static int
+gf_inv_row(const uint8_t *src, uint32_t n, uint8_t *dst)
+{
+    uint32_t i, q;
+
+    for (i = 0; i < n; i++) {
+        q = ec_method_gf_div(1, src[i]);
+        if (q == 0 || q >= EC_GF_SIZE)
+            return -EINVAL;
+        dst[i] = (uint8_t)q;
+    }
+    return 0;
+}
+
+/* ------------------------------------------- consistency check (scrub) */
+
+/* A host-only build links a stand-in of the device layer that may lack the
+ * check's device entry (tests/c/ecd_stub.c): the reference is weak, and
+ * without the symbol ec_method_verify_device is -ENODEV. */
+extern __typeof__(ecd_verify) ecd_verify __attribute__((weak));
+
+/* Arguments both entry points share: the masks, the pointer arrays and the
+ * alignment of bad[].  rows[] gets the bricks of mask, bricks[] / *nc those
+ * of check_mask. */
+static int
+verify_args(ec_matrix_list_t *list, uintptr_t mask, const void *const *in, uintptr_t check_mask,
+            const void *const *check, const uint32_t *bad, uint32_t *rows, uint8_t *bricks,
+            uint32_t *nc)
+{
+    uint32_t i, c = 0;
+
+    if (!list || !CTX(list) || !in || !check || !bad || ((uintptr_t)bad & 3u))
+        return -EINVAL;
+    rows_from_mask(mask, rows);
+    if (!mask_rows_ok(list, mask, rows))
+        return -EINVAL;
+    if (check_mask == 0 || (check_mask >> list->rows) != 0 || (check_mask & mask) != 0)
+        return -EINVAL;
+    for (i = 0; i < list->rows; i++)
+        if ((check_mask >> i) & 1)
+            bricks[c++] = (uint8_t)i;
+    *nc = c;
+    return 0;
+}
+
+/* verify_args does not look into in[] and check[]: a NULL entry is rejected
+ * by both entry points after the zero-stripes return, so a call of no stripes
+ * with one returns 0. */
+static int
+verify_entries_ok(const void *const *in, uint32_t k, const void *const *check, uint32_t nc)
+{
+    uint32_t i;
+
+    for (i = 0; i < k; i++)
+        if (!in[i])
+            return 0;
+    for (i = 0; i < nc; i++)
+        if (!check[i])
+            return 0;
+    return 1;
+}
+
+/* check_pass found rows that differ: their bricks are the stripe's flags */
+static int
+verify_differs(void *arg, uint64_t t, uint32_t diff, const uint8_t *pred, size_t pred_stride,
+               uint32_t *flag)
+{
+    const uint8_t *bricks = (const uint8_t *)arg;
+
+    (void)t;
+    (void)pred;
+    (void)pred_stride;
+    for (; diff; diff &= diff - 1)
+        *flag |= 1u << bricks[__builtin_ctz(diff)];
+    return 0;
+}
+
+static int32_t
+ecm_verify_impl(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask, const void *const *in,
+                uintptr_t check_mask, const void *const *check, uint32_t *bad, uint64_t *nbad)
+{
+    ecd_combine_desc_t d;
+    uint32_t rows[ECM_MAX_K], nc = 0, nt = 0;
+    uint8_t bricks[ECM_MAX_N];
+    int rc;
+
+    rc = verify_args(list, mask, in, check_mask, check, bad, rows, bricks, &nc);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    if (!verify_entries_ok(in, list->columns, check, nc) ||
+        !scrub_on_host(in, list->columns, check, nc, NULL, 0, bad, NULL))
+        return -EINVAL;
+    rc = heal_pattern(list, mask, rows, check_mask, d.pat, &nt);
+    if (rc)
+        return rc;
+    desc_init_frags(&d, list->columns, nt, 0);
+    return check_pass(CTX(list)->isa, &d, nstripes, in, check, bad, nbad, verify_differs, bricks);
+}
+
+static int32_t
+ecm_verify_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                       uintptr_t mask, const void *const *in, uintptr_t check_mask,
+                       const void *const *check, uint32_t *bad)
+{
+    ecd_combine_desc_t d;
+    uint32_t rows[ECM_MAX_K], nc = 0, nt = 0, p;
+    uint8_t bricks[ECM_MAX_N];
+    int rc;
+
+    rc = verify_args(list, mask, in, check_mask, check, bad, rows, bricks, &nc);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    if (!verify_entries_ok(in, list->columns, check, nc) ||
+        !scrub_on_device(device, in, list->columns, check, nc, NULL, 0, bad, NULL))
+        return -EINVAL;
+    if (!ecd_verify)
+        return -ENODEV;
+    rc = heal_pattern(list, mask, rows, check_mask, d.pat, &nt);
+    if (rc)
+        return rc;
+    desc_init_frags(&d, list->columns, nt, nstripes);
+    for (p = 0; p < d.k; p++)
+        d.in_base[p] = in[p];
+    return ecd_verify(device, stream, &d, check, bricks, bad);
+}
+
+/* ------------------------------------------- locating the damaged brick */
+
+/* Weak like ecd_verify: without the symbol ec_method_locate_device is
+ * -ENODEV. */
+extern __typeof__(ecd_locate) ecd_locate __attribute__((weak));
+
+/* The calls that name a brick want two bricks beside the basis (avail_sets'
+ * spare), the `two` ones four.
+ *
+ * The prediction matrix G (nr x k, in d->pat after its k source bytes) and
+ * the ratios q[c][b] = G[c][b] / G[c0][b] of the rows after the first, (nr -
+ * 1) x k.  The code is MDS, so no entry of G is zero.  d becomes the
+ * prediction of R from B over nstripes, as the device calls launch it. */
+static int
+locate_tables(ec_matrix_list_t *list, const ecm_locate_sets_t *s, uint64_t nstripes,
+              ecd_combine_desc_t *d, uint8_t *ratio)
 {
     const uint32_t k = list->columns;
     uint32_t nt = 0, r, p, q;
     int rc;
 
-    memset(d, 0, offsetof(ecd_combine_desc_t, pat));
     rc = heal_pattern(list, s->bmask, s->rows, s->rmask, d->pat, &nt);
     if (rc)
         return rc;
@@ -2862,12 +3013,9 @@ locate_tables(ec_matrix_list_t *list, const ecm_locate_sets_t *s, ecd_combine_de
                 return -EINVAL;
             ratio[(r - 1) * k + p] = (uint8_t)q;
         }
-    d->k = k;
-    d->rows = nt;
-    d->npatterns = 1;
-    d->pat_bytes = k + nt * k;
-    d->in_stride = EC_METHOD_CHUNK_SIZE;
-    d->out_stride = EC_METHOD_CHUNK_SIZE;
+    desc_init_frags(d, k, nt, nstripes);
+    for (p = 0; p < k; p++)
+        d->in_base[p] = s->in[p];
     return 0;
 }
 
@@ -2911,14 +3059,7 @@ locate_classify(int isa, const ecm_locate_sets_t *s, uint32_t k, const uint8_t *
         return 0;
     }
     *out = EC_MI355X_LOCATE_MANY;
-    memset(&m, 0, offsetof(ecd_combine_desc_t, pat));
-    m.k = 1;
-    m.rows = 1;
-    m.nstripes = 1;
-    m.npatterns = 1;
-    m.pat_bytes = 2;
-    m.in_stride = EC_METHOD_CHUNK_SIZE;
-    m.out_stride = EC_METHOD_CHUNK_SIZE;
+    desc_init_frags(&m, 1, 1, 1);
     m.in_base[0] = syn;
     m.out_base[0] = prod;
     m.pat[0] = 0;
@@ -2994,14 +3135,7 @@ syn_fits(int isa, const uint8_t *syn, uint32_t row, uint32_t terms, uint32_t i0,
 
     if (c0 >= EC_GF_SIZE || c1 >= EC_GF_SIZE)
         return -EINVAL;
-    memset(&m, 0, offsetof(ecd_combine_desc_t, pat));
-    m.k = terms;
-    m.rows = 1;
-    m.nstripes = 1;
-    m.npatterns = 1;
-    m.pat_bytes = 2 * terms;
-    m.in_stride = EC_METHOD_CHUNK_SIZE;
-    m.out_stride = EC_METHOD_CHUNK_SIZE;
+    desc_init_frags(&m, terms, 1, 1);
     m.in_base[0] = syn + (size_t)i0 * EC_METHOD_CHUNK_SIZE;
     m.in_base[1] = syn + (size_t)i1 * EC_METHOD_CHUNK_SIZE;
     m.out_base[0] = prod;
@@ -3101,75 +3235,65 @@ locate2_classify(int isa, const ecm_locate_sets_t *s, uint32_t k, const uint8_t 
     return 0;
 }
 
+/* What the host pass knows when a stripe differs */
+typedef struct {
+    int isa, two;
+    const ecm_locate_sets_t *s;
+    uint32_t k;
+    const uint8_t *G, *ratio;
+} ecm_locate_ctx_t;
+
+/* check_pass found a stripe that differs, the rare path: its syndromes are
+ * prediction ^ stored, and the classifier names the brick or the pair */
+static int
+locate_differs(void *arg, uint64_t t, uint32_t diff, const uint8_t *pred, size_t pred_stride,
+               uint32_t *flag)
+{
+    const ecm_locate_ctx_t *c = (const ecm_locate_ctx_t *)arg;
+    uint8_t syn[ECM_MAX_N * EC_METHOD_CHUNK_SIZE] __attribute__((aligned(64)));
+    const uint8_t *st;
+    uint32_t r, p;
+
+    (void)diff;
+    for (r = 0; r < c->s->nr; r++) {
+        st = (const uint8_t *)c->s->check[r] + t * EC_METHOD_CHUNK_SIZE;
+        for (p = 0; p < EC_METHOD_CHUNK_SIZE; p++)
+            syn[r * EC_METHOD_CHUNK_SIZE + p] = pred[r * pred_stride + p] ^ st[p];
+    }
+    return c->two ? locate2_classify(c->isa, c->s, c->k, c->G, c->ratio, syn, flag)
+                  : locate_classify(c->isa, c->s, c->k, c->ratio, syn, flag);
+}
+
 /* Both host calls: `two` = ec_method_locate2 (a >= k + 4, pairs named). */
 static int32_t
 locate_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
             const void *const *frags, uint32_t *loc, uint64_t *nbad, int two)
 {
     ecm_locate_sets_t s;
+    ecm_locate_ctx_t c;
     ecd_combine_desc_t d;
     uint8_t ratio[ECM_MAX_N * ECM_MAX_K];
-    uint8_t syn[ECM_MAX_N * EC_METHOD_CHUNK_SIZE] __attribute__((aligned(64)));
-    uint32_t p, r, k, dirty;
-    uint64_t s0, t, n, count = 0;
-    uint8_t *scratch;
     int rc;
 
-    rc = locate_args(list, avail_mask, frags, loc, &s);
+    rc = avail_sets(list, avail_mask, frags, loc, 2, &s);
     if (rc)
         return rc;
     if (two && s.nr < 4)
         return -EINVAL;
     if (nstripes == 0)
         return 0;
-    k = list->columns;
-    /* host entry point: device buffers go to _device */
-    if (!bufs_on(s.in, k, -1) || !bufs_on(s.check, s.nr, -1) || ecd_ptr_device(loc) >= 0)
+    if (!scrub_on_host(s.in, list->columns, s.check, s.nr, NULL, 0, loc, NULL))
         return -EINVAL;
-    rc = locate_tables(list, &s, &d, ratio);
+    rc = locate_tables(list, &s, 0, &d, ratio);
     if (rc)
         return rc;
-    /* as ecm_verify_impl: the CPU engine predicts a few dozen stripes of the
-     * check bricks; a stripe with a mismatch then takes the slow path */
-    scratch = (uint8_t *)malloc((size_t)ECM_VERIFY_STRIPES * s.nr * EC_METHOD_CHUNK_SIZE);
-    if (!scratch)
-        return -ENOMEM;
-    for (r = 0; r < s.nr; r++)
-        d.out_base[r] = scratch + (size_t)r * ECM_VERIFY_STRIPES * EC_METHOD_CHUNK_SIZE;
-    for (s0 = 0; s0 < nstripes && rc == 0; s0 += n) {
-        n = nstripes - s0 < ECM_VERIFY_STRIPES ? nstripes - s0 : ECM_VERIFY_STRIPES;
-        d.nstripes = n;
-        for (p = 0; p < k; p++)
-            d.in_base[p] = (const uint8_t *)s.in[p] + s0 * EC_METHOD_CHUNK_SIZE;
-        rc = ecc_combine(CTX(list)->isa, &d);
-        if (rc)
-            break;
-        for (t = 0; t < n && rc == 0; t++) {
-            dirty = 0;
-            for (r = 0; r < s.nr; r++)
-                dirty |= memcmp((const uint8_t *)d.out_base[r] + t * EC_METHOD_CHUNK_SIZE,
-                                (const uint8_t *)s.check[r] + (s0 + t) * EC_METHOD_CHUNK_SIZE,
-                                EC_METHOD_CHUNK_SIZE) != 0;
-            if (!dirty) {
-                loc[s0 + t] = 0;
-                continue;
-            }
-            for (r = 0; r < s.nr; r++) {
-                const uint8_t *pr = (const uint8_t *)d.out_base[r] + t * EC_METHOD_CHUNK_SIZE;
-                const uint8_t *st = (const uint8_t *)s.check[r] + (s0 + t) * EC_METHOD_CHUNK_SIZE;
-                for (p = 0; p < EC_METHOD_CHUNK_SIZE; p++)
-                    syn[r * EC_METHOD_CHUNK_SIZE + p] = pr[p] ^ st[p];
-            }
-            rc = two ? locate2_classify(CTX(list)->isa, &s, k, d.pat + k, ratio, syn,
-                                        &loc[s0 + t])
-                     : locate_classify(CTX(list)->isa, &s, k, ratio, syn, &loc[s0 + t]);
-            count++;
-        }
-    }
-    free(scratch);
-    if (rc == 0 && nbad)
-        *nbad = count;
-    return rc;
+    c.isa = CTX(list)->isa;
+    c.two = two;
+    c.s = &s;
+    c.k = list->columns;
+    c.G = d.pat + c.k;
+    c.ratio = ratio;
+    return check_pass(c.isa, &d, nstripes, s.in, s.check, loc, nbad, locate_differs, &c);
 }
 
 /* Both device calls: `two` = ec_method_locate2_device. */
@@ -3181,37 +3305,24 @@ locate_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripe
     ecd_combine_desc_t d;
     uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ratio1[ECM_MAX_N * ECM_MAX_K];
     uint8_t pinv[ECM_MAX_K * (ECM_MAX_K - 1) / 2 * 4];
-    uint32_t p;
     int rc;
 
-    rc = locate_args(list, avail_mask, frags, loc, &s);
+    rc = avail_sets(list, avail_mask, frags, loc, 2, &s);
     if (rc)
         return rc;
     if (two && s.nr < 4)
         return -EINVAL;
     if (nstripes == 0)
         return 0;
-    /* device entry point: every buffer lives on `device` */
-    if (device < 0)
-        return -EINVAL;
-    for (p = 0; p < list->columns; p++)
-        if (ecd_ptr_device(s.in[p]) != device)
-            return -EINVAL;
-    for (p = 0; p < s.nr; p++)
-        if (ecd_ptr_device(s.check[p]) != device)
-            return -EINVAL;
-    if (ecd_ptr_device(loc) != device)
+    if (!scrub_on_device(device, s.in, list->columns, s.check, s.nr, NULL, 0, loc, NULL))
         return -EINVAL;
     if (two ? !ecd_locate2 : !ecd_locate)
         return -ENODEV;
-    rc = locate_tables(list, &s, &d, ratio);
+    rc = locate_tables(list, &s, nstripes, &d, ratio);
     if (rc == 0 && two)
         rc = locate2_tables(d.k, s.nr, d.pat + d.k, ratio1, pinv);
     if (rc)
         return rc;
-    d.nstripes = nstripes;
-    for (p = 0; p < d.k; p++)
-        d.in_base[p] = s.in[p];
     if (two)
         return ecd_locate2(device, stream, &d, s.check, s.cb, s.bb, ratio, ratio1, pinv, loc);
     return ecd_locate(device, stream, &d, s.check, s.cb, s.bb, ratio, loc);
@@ -3224,21 +3335,6 @@ locate_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripe
 extern __typeof__(ecd_decode_checked) ecd_decode_checked __attribute__((weak));
 extern __typeof__(ecd_decode_checked2) ecd_decode_checked2 __attribute__((weak));
 
-/* The mask stripe t is decoded with: B, or B_S = B without the basis bricks
- * loc[t] names and with as many of the lowest check bricks it does not name
- * (for one basis brick i that is B_i: B without i and with c0).  MANY is bit
- * 31 and no mask has a bit there. */
-static uintptr_t
-checked_mask(const ecm_locate_sets_t *s, uint32_t w)
-{
-    uintptr_t named = (uintptr_t)w & s->bmask, spare = s->rmask & ~(uintptr_t)w;
-    uintptr_t mask = s->bmask & ~named;
-
-    for (; named; named &= named - 1, spare &= spare - 1)
-        mask |= spare & (~spare + 1);
-    return mask;
-}
-
 /* Both host calls: `two` = ec_method_decode_checked2 (a >= k + 4, loc[] is
  * ec_method_locate2's and a pair is decoded around). */
 static int32_t
@@ -3247,52 +3343,40 @@ decode_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_m
                     uint64_t *nmany, int two)
 {
     ecm_locate_sets_t s;
+    ecm_mask_run_t run = {0};
     ecd_combine_desc_t d;
-    uint64_t t, t1, bad = 0, many = 0;
-    uintptr_t mask, cur = 0;
+    uint64_t bad = 0;
     uint32_t k, r, b;
     int rc;
 
-    rc = locate_args(list, avail_mask, frags, loc, &s);
+    rc = avail_sets(list, avail_mask, frags, loc, 2, &s);
     if (rc)
         return rc;
     if (!out || (two && s.nr < 4))
         return -EINVAL;
     if (nstripes == 0)
         return 0;
-    /* host entry point: device buffers go to _device (locate_host looks at
-     * the fragments and loc before it writes) */
-    if (ecd_ptr_device(out) >= 0)
+    /* locate_host looks at the fragments and loc before it writes */
+    if (!scrub_on_host(NULL, 0, NULL, 0, NULL, 0, out, NULL))
         return -EINVAL;
     rc = locate_host(list, nstripes, avail_mask, frags, loc, &bad, two);
     if (rc)
         return rc;
-    /* a run of stripes that share a decode mask is one combine; the inverses
-     * come from the list's matrix cache */
+    /* the inverses come from the list's matrix cache */
     k = list->columns;
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
-    d.k = k;
-    d.rows = k;
-    d.npatterns = 1;
-    d.pat_bytes = k + k * k;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = (uint64_t)k * EC_METHOD_CHUNK_SIZE;
-    for (t = 0; t < nstripes; t = t1) {
-        mask = checked_mask(&s, loc[t]);
-        for (t1 = t; t1 < nstripes && checked_mask(&s, loc[t1]) == mask; t1++)
-            many += loc[t1] == EC_MI355X_LOCATE_MANY;
-        if (mask != cur) {
-            rc = mask_pattern(list, mask, d.pat);
-            if (rc)
-                return rc;
-            cur = mask;
-        }
-        d.nstripes = t1 - t;
+    desc_init(&d, k, k, 0, EC_METHOD_CHUNK_SIZE, (uint64_t)k * EC_METHOD_CHUNK_SIZE);
+    while (mask_run_next(&run, &s, loc, nstripes)) {
+        rc = mask_pattern(list, run.mask, d.pat);
+        if (rc)
+            return rc;
+        d.nstripes = run.t1 - run.t;
+        /* mask_pattern's inputs are indexed by brick */
         for (b = 0; b < list->rows; b++)
-            d.in_base[b] = (mask >> b) & 1 ? (const uint8_t *)frags[b] + t * EC_METHOD_CHUNK_SIZE
-                                           : NULL;
+            d.in_base[b] = (run.mask >> b) & 1
+                               ? (const uint8_t *)frags[b] + run.t * EC_METHOD_CHUNK_SIZE
+                               : NULL;
         for (r = 0; r < k; r++)
-            d.out_base[r] = (uint8_t *)out + (t * k + r) * EC_METHOD_CHUNK_SIZE;
+            d.out_base[r] = (uint8_t *)out + (run.t * k + r) * EC_METHOD_CHUNK_SIZE;
         rc = ecc_combine(CTX(list)->isa, &d);
         if (rc)
             return rc;
@@ -3300,7 +3384,7 @@ decode_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_m
     if (nbad)
         *nbad = bad;
     if (nmany)
-        *nmany = many;
+        *nmany = run.many;
     return 0;
 }
 
@@ -3315,48 +3399,30 @@ decode_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t
     uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ratio1[ECM_MAX_N * ECM_MAX_K], ginv[2 * ECM_MAX_K];
     uint8_t pinv[ECM_MAX_K * (ECM_MAX_K - 1) / 2 * 4];
     uint8_t pat[ECM_MAX_K + ECM_MAX_K * ECM_MAX_K];
-    uint32_t p, q, r;
     int rc;
 
-    rc = locate_args(list, avail_mask, frags, loc, &s);
+    rc = avail_sets(list, avail_mask, frags, loc, 2, &s);
     if (rc)
         return rc;
     if (!out || (two && s.nr < 4))
         return -EINVAL;
     if (nstripes == 0)
         return 0;
-    /* device entry point: every buffer lives on `device` */
-    if (device < 0)
-        return -EINVAL;
-    for (p = 0; p < list->columns; p++)
-        if (ecd_ptr_device(s.in[p]) != device)
-            return -EINVAL;
-    for (p = 0; p < s.nr; p++)
-        if (ecd_ptr_device(s.check[p]) != device)
-            return -EINVAL;
-    if (ecd_ptr_device(loc) != device || ecd_ptr_device(out) != device)
+    if (!scrub_on_device(device, s.in, list->columns, s.check, s.nr, NULL, 0, loc, out))
         return -EINVAL;
     if (two ? !ecd_decode_checked2 : !ecd_decode_checked)
         return -ENODEV;
-    rc = locate_tables(list, &s, &d, ratio);
+    rc = locate_tables(list, &s, nstripes, &d, ratio);
     if (rc == 0 && two)
         rc = locate2_tables(d.k, s.nr, d.pat + d.k, ratio1, pinv);
     if (rc == 0)
         rc = mask_pattern(list, s.bmask, pat);
-    if (rc)
-        return rc;
     /* 1 / G[0][p]: the error of basis position p from the first syndrome;
      * with `two` also 1 / G[1][p], for a pair whose check brick is row 0 */
-    for (r = 0; r < (two ? 2u : 1u); r++)
-        for (p = 0; p < d.k; p++) {
-            q = ec_method_gf_div(1, d.pat[d.k + r * d.k + p]);
-            if (q == 0 || q >= EC_GF_SIZE)
-                return -EINVAL;
-            ginv[r * d.k + p] = (uint8_t)q;
-        }
-    d.nstripes = nstripes;
-    for (p = 0; p < d.k; p++)
-        d.in_base[p] = s.in[p];
+    if (rc == 0)
+        rc = gf_inv_row(d.pat + d.k, (two ? 2 : 1) * d.k, ginv);
+    if (rc)
+        return rc;
     if (two)
         return ecd_decode_checked2(device, stream, &d, s.check, s.cb, s.bb, ratio, ratio1, pinv,
                                    pat + d.k, ginv, out, loc);
@@ -3370,29 +3436,6 @@ decode_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t
  * -ENODEV. */
 extern __typeof__(ecd_heal_checked) ecd_heal_checked __attribute__((weak));
 
-/* What both entry points check beside locate_args: the targets are bricks of
- * the volume outside avail_mask, each with a buffer.  *nt gets their number. */
-static int
-heal_checked_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags,
-                  uintptr_t target_mask, void *const *out, const uint32_t *loc,
-                  ecm_locate_sets_t *s, uint32_t *nt)
-{
-    uint32_t j;
-    int rc;
-
-    rc = locate_args(list, avail_mask, frags, loc, s);
-    if (rc)
-        return rc;
-    if (!out || target_mask == 0 || (target_mask >> list->rows) != 0 ||
-        (target_mask & avail_mask) != 0)
-        return -EINVAL;
-    *nt = popcount_mask(target_mask);
-    for (j = 0; j < *nt; j++)
-        if (!out[j])
-            return -EINVAL;
-    return 0;
-}
-
 /* The host call.  The stripes are healed in runs that share a mask, as
  * decode_checked_host decodes them; loc[] is ec_method_locate's. */
 static int32_t
@@ -3401,53 +3444,42 @@ heal_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mas
                   uint32_t *loc, uint64_t *nbad, uint64_t *nmany)
 {
     ecm_locate_sets_t s;
+    ecm_mask_run_t run = {0};
     ecd_combine_desc_t d;
-    uint64_t t, t1, bad = 0, many = 0;
-    uintptr_t mask, cur = 0;
+    uint64_t bad = 0;
     uint32_t rows[ECM_MAX_K], nt = 0, n, b, p, j;
     int rc;
 
-    rc = heal_checked_args(list, avail_mask, frags, target_mask, out, loc, &s, &nt);
+    rc = avail_sets(list, avail_mask, frags, loc, 2, &s);
     if (rc)
         return rc;
+    if (!heal_targets_ok(list, avail_mask, target_mask, out, &nt))
+        return -EINVAL;
     if (nstripes == 0)
         return 0;
-    /* host entry point: device buffers go to _device (locate_host looks at
-     * the fragments and loc before it writes) */
-    if (!bufs_on((const void *const *)out, nt, -1))
+    /* locate_host looks at the fragments and loc before it writes */
+    if (!scrub_on_host(NULL, 0, NULL, 0, out, nt, NULL, NULL))
         return -EINVAL;
     rc = locate_host(list, nstripes, avail_mask, frags, loc, &bad, 0);
     if (rc)
         return rc;
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
-    d.k = list->columns;
-    d.rows = nt;
-    d.npatterns = 1;
-    d.pat_bytes = d.k + nt * d.k;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
-    for (t = 0; t < nstripes; t = t1) {
-        mask = checked_mask(&s, loc[t]);
-        for (t1 = t; t1 < nstripes && checked_mask(&s, loc[t1]) == mask; t1++)
-            many += loc[t1] == EC_MI355X_LOCATE_MANY;
-        if (mask != cur) {
-            rows_from_mask(mask, rows);
-            if (!mask_rows_ok(list, mask, rows))
-                return -EINVAL;
-            rc = heal_pattern(list, mask, rows, target_mask, d.pat, &n);
-            if (rc)
-                return rc;
-            if (n != nt)
-                return -EINVAL;
-            cur = mask;
-        }
-        d.nstripes = t1 - t;
+    desc_init_frags(&d, list->columns, nt, 0);
+    while (mask_run_next(&run, &s, loc, nstripes)) {
+        rows_from_mask(run.mask, rows);
+        if (!mask_rows_ok(list, run.mask, rows))
+            return -EINVAL;
+        rc = heal_pattern(list, run.mask, rows, target_mask, d.pat, &n);
+        if (rc)
+            return rc;
+        if (n != nt)
+            return -EINVAL;
+        d.nstripes = run.t1 - run.t;
         /* heal_pattern's input p is the p-th brick of the mask */
         for (b = 0, p = 0; b < list->rows; b++)
-            if ((mask >> b) & 1)
-                d.in_base[p++] = (const uint8_t *)frags[b] + t * EC_METHOD_CHUNK_SIZE;
+            if ((run.mask >> b) & 1)
+                d.in_base[p++] = (const uint8_t *)frags[b] + run.t * EC_METHOD_CHUNK_SIZE;
         for (j = 0; j < nt; j++)
-            d.out_base[j] = (uint8_t *)out[j] + t * EC_METHOD_CHUNK_SIZE;
+            d.out_base[j] = (uint8_t *)out[j] + run.t * EC_METHOD_CHUNK_SIZE;
         rc = ecc_combine(CTX(list)->isa, &d);
         if (rc)
             return rc;
@@ -3455,7 +3487,7 @@ heal_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mas
     if (nbad)
         *nbad = bad;
     if (nmany)
-        *nmany = many;
+        *nmany = run.many;
     return 0;
 }
 
@@ -3470,31 +3502,21 @@ heal_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t n
     ecd_combine_desc_t d;
     uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ginv[ECM_MAX_K];
     uint8_t pat[ECM_MAX_K + ECM_MAX_N * ECM_MAX_K];
-    uint32_t nt = 0, n, p, q;
+    uint32_t nt = 0, n;
     int rc;
 
-    rc = heal_checked_args(list, avail_mask, frags, target_mask, out, loc, &s, &nt);
+    rc = avail_sets(list, avail_mask, frags, loc, 2, &s);
     if (rc)
         return rc;
+    if (!heal_targets_ok(list, avail_mask, target_mask, out, &nt))
+        return -EINVAL;
     if (nstripes == 0)
         return 0;
-    /* device entry point: every buffer lives on `device` */
-    if (device < 0)
-        return -EINVAL;
-    for (p = 0; p < list->columns; p++)
-        if (ecd_ptr_device(s.in[p]) != device)
-            return -EINVAL;
-    for (p = 0; p < s.nr; p++)
-        if (ecd_ptr_device(s.check[p]) != device)
-            return -EINVAL;
-    for (p = 0; p < nt; p++)
-        if (ecd_ptr_device(out[p]) != device)
-            return -EINVAL;
-    if (ecd_ptr_device(loc) != device)
+    if (!scrub_on_device(device, s.in, list->columns, s.check, s.nr, out, nt, loc, NULL))
         return -EINVAL;
     if (!ecd_heal_checked)
         return -ENODEV;
-    rc = locate_tables(list, &s, &d, ratio);
+    rc = locate_tables(list, &s, nstripes, &d, ratio);
     if (rc == 0)
         rc = heal_pattern(list, s.bmask, s.rows, target_mask, pat, &n);
     if (rc)
@@ -3502,15 +3524,9 @@ heal_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t n
     if (n != nt)
         return -EINVAL;
     /* 1 / G[0][p]: the error of basis position p from the first syndrome */
-    for (p = 0; p < d.k; p++) {
-        q = ec_method_gf_div(1, d.pat[d.k + p]);
-        if (q == 0 || q >= EC_GF_SIZE)
-            return -EINVAL;
-        ginv[p] = (uint8_t)q;
-    }
-    d.nstripes = nstripes;
-    for (p = 0; p < d.k; p++)
-        d.in_base[p] = s.in[p];
+    rc = gf_inv_row(d.pat + d.k, d.k, ginv);
+    if (rc)
+        return rc;
     return ecd_heal_checked(device, stream, &d, s.check, s.cb, s.bb, ratio, nt, pat + d.k, ginv,
                             out, loc);
 }
@@ -3523,33 +3539,22 @@ heal_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t n
 extern __typeof__(ecd_decode_verified) ecd_decode_verified __attribute__((weak));
 extern __typeof__(ecd_heal_verified) ecd_heal_verified __attribute__((weak));
 
-/* What the four entry points check: locate_args' rules with one brick beside
- * the basis instead of two, and an output.  With `heal`, out is the list of
- * target fragments and heal_checked_args' rules for target_mask hold; *nt
- * gets the number of targets. */
+/* What the four entry points check: one brick beside the basis is enough,
+ * and an output.  With `heal`, out is the list of target fragments and
+ * heal_targets_ok's rule holds; *nt gets the number of targets, else 0. */
 static int
 verified_args(ec_matrix_list_t *list, uintptr_t avail_mask, const void *const *frags, int heal,
               uintptr_t target_mask, const void *out, const uint32_t *bad,
               ecm_locate_sets_t *s, uint32_t *nt)
 {
-    void *const *outs = (void *const *)out;
-    uint32_t j;
     int rc;
 
     rc = avail_sets(list, avail_mask, frags, bad, 1, s);
     if (rc)
         return rc;
-    if (!out)
-        return -EINVAL;
     *nt = 0;
-    if (!heal)
-        return 0;
-    if (target_mask == 0 || (target_mask >> list->rows) != 0 || (target_mask & avail_mask) != 0)
+    if (heal ? !heal_targets_ok(list, avail_mask, target_mask, (void *const *)out, nt) : !out)
         return -EINVAL;
-    *nt = popcount_mask(target_mask);
-    for (j = 0; j < *nt; j++)
-        if (!outs[j])
-            return -EINVAL;
     return 0;
 }
 
@@ -3571,12 +3576,11 @@ verified_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
         return rc;
     if (nstripes == 0)
         return 0;
-    /* host entry point: device buffers go to _device (ecm_verify_impl looks
-     * at the fragments and bad before it writes) */
-    if (heal ? !bufs_on((const void *const *)outs, nt, -1) : ecd_ptr_device(out) >= 0)
+    /* ecm_verify_impl looks at the fragments and bad before it writes; nt is
+     * 0 for the read, whose out is one buffer */
+    if (!scrub_on_host(NULL, 0, NULL, 0, outs, nt, heal ? NULL : out, NULL))
         return -EINVAL;
     k = list->columns;
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
     if (heal) {
         rc = heal_pattern(list, s.bmask, s.rows, target_mask, d.pat, &n);
         if (rc == 0 && n != nt)
@@ -3589,13 +3593,8 @@ verified_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
     rc = ecm_verify_impl(list, nstripes, s.bmask, s.in, s.rmask, s.check, bad, nbad);
     if (rc)
         return rc;
-    d.k = k;
-    d.rows = heal ? nt : k;
-    d.nstripes = nstripes;
-    d.npatterns = 1;
-    d.pat_bytes = k + d.rows * k;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = heal ? EC_METHOD_CHUNK_SIZE : (uint64_t)k * EC_METHOD_CHUNK_SIZE;
+    desc_init(&d, k, heal ? nt : k, nstripes, EC_METHOD_CHUNK_SIZE,
+              heal ? EC_METHOD_CHUNK_SIZE : (uint64_t)k * EC_METHOD_CHUNK_SIZE);
     if (heal) {
         /* heal_pattern's input p is the p-th brick of the mask */
         for (b = 0; b < k; b++)
@@ -3631,23 +3630,12 @@ verified_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstri
         return rc;
     if (nstripes == 0)
         return 0;
-    /* device entry point: every buffer lives on `device` */
-    if (device < 0)
-        return -EINVAL;
-    for (p = 0; p < list->columns; p++)
-        if (ecd_ptr_device(s.in[p]) != device)
-            return -EINVAL;
-    for (p = 0; p < s.nr; p++)
-        if (ecd_ptr_device(s.check[p]) != device)
-            return -EINVAL;
-    for (p = 0; p < nt; p++)
-        if (ecd_ptr_device(outs[p]) != device)
-            return -EINVAL;
-    if (ecd_ptr_device(bad) != device || (!heal && ecd_ptr_device(out) != device))
+    /* nt is 0 for the read, whose out is one buffer */
+    if (!scrub_on_device(device, s.in, list->columns, s.check, s.nr, outs, nt, bad,
+                         heal ? NULL : out))
         return -EINVAL;
     if (heal ? !ecd_heal_verified : !ecd_decode_verified)
         return -ENODEV;
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
     rc = heal_pattern(list, s.bmask, s.rows, s.rmask, d.pat, &nc);
     if (rc == 0 && nc != s.nr)
         rc = -EINVAL;
@@ -3660,13 +3648,7 @@ verified_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstri
     }
     if (rc)
         return rc;
-    d.k = list->columns;
-    d.rows = nc;
-    d.nstripes = nstripes;
-    d.npatterns = 1;
-    d.pat_bytes = d.k + nc * d.k;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    desc_init_frags(&d, list->columns, nc, nstripes);
     for (p = 0; p < d.k; p++)
         d.in_base[p] = s.in[p];
     if (heal)
@@ -3690,26 +3672,20 @@ typedef struct {
     uint8_t coef[ECM_MAX_N * ECM_MAX_K];
 } ecm_repair_sets_t;
 
-/* `extra`: the bricks wanted beside k, 1 for repair and 2 for repair2 (k
- * others must remain once the named ones are removed). */
+/* avail_sets with the bricks wanted beside k, 1 for repair and 2 for repair2
+ * (k others must remain once the named ones are removed); bset[] is then the
+ * basis and the first check brick. */
 static int
 repair_args(ec_matrix_list_t *list, uintptr_t avail_mask, void *const *frags,
-            const uint32_t *loc, uint32_t extra, ecm_repair_sets_t *s)
+            const uint32_t *loc, int two, ecm_locate_sets_t *ls, ecm_repair_sets_t *s)
 {
-    uint32_t i, nb = 0;
+    int rc;
 
-    if (!list || !CTX(list) || !frags || !loc || ((uintptr_t)loc & 3u))
-        return -EINVAL;
-    if ((avail_mask >> list->rows) != 0 || popcount_mask(avail_mask) < list->columns + extra)
-        return -EINVAL;
-    for (i = 0; i < list->rows; i++) {
-        if (!((avail_mask >> i) & 1))
-            continue;
-        if (!frags[i])
-            return -EINVAL;
-        if (nb <= list->columns)
-            s->bset[nb++] = (uint8_t)i;
-    }
+    rc = avail_sets(list, avail_mask, (const void *const *)frags, loc, two ? 2 : 1, ls);
+    if (rc)
+        return rc;
+    memcpy(s->bset, ls->bb, list->columns);
+    s->bset[list->columns] = ls->cb[0];
     return 0;
 }
 
@@ -3785,32 +3761,26 @@ repair_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
             int two)
 {
     ecm_repair_sets_t s;
+    ecm_locate_sets_t ls;
     ecd_combine_desc_t d;
     uint8_t pbricks[ECM_MAX_K], pcoef[2 * ECM_MAX_K];
     uint32_t i, j, p, q, k, w, pw = 0;
     uint64_t t, e, done = 0, skipped = 0;
     int rc;
 
-    rc = repair_args(list, avail_mask, frags, loc, two ? 2 : 1, &s);
+    rc = repair_args(list, avail_mask, frags, loc, two, &ls, &s);
     if (rc)
         return rc;
     if (nstripes == 0)
         return 0;
     k = list->columns;
-    /* host entry point: device buffers go to _device */
-    for (i = 0; i < list->rows; i++)
-        if (((avail_mask >> i) & 1) && ecd_ptr_device(frags[i]) >= 0)
-            return -EINVAL;
-    if (ecd_ptr_device(loc) >= 0)
+    if (!scrub_on_host(ls.in, k, ls.check, ls.nr, NULL, 0, loc, NULL))
         return -EINVAL;
     rc = repair_tables(list, avail_mask, &s);
     if (rc)
         return rc;
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
-    d.k = k;
-    d.npatterns = 1;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    /* rows and pat_bytes are the run's: one row or two */
+    desc_init_frags(&d, k, 0, 0);
     for (p = 0; p < k; p++)
         d.pat[p] = (uint8_t)p;
     /* clean stripes cost the scan; a run of stripes naming one brick is one
@@ -3883,21 +3853,14 @@ repair_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripe
     uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ratio1[ECM_MAX_N * ECM_MAX_K];
     uint8_t pinv[ECM_MAX_K * (ECM_MAX_K - 1) / 2 * 4], ginv[2 * ECM_MAX_K];
     const uint8_t *G;
-    uint32_t i, v;
     int rc;
 
-    rc = repair_args(list, avail_mask, frags, loc, two ? 2 : 1, &s);
+    rc = repair_args(list, avail_mask, frags, loc, two, &ls, &s);
     if (rc)
         return rc;
     if (nstripes == 0)
         return 0;
-    /* device entry point: every buffer lives on `device` */
-    if (device < 0)
-        return -EINVAL;
-    for (i = 0; i < list->rows; i++)
-        if (((avail_mask >> i) & 1) && ecd_ptr_device(frags[i]) != device)
-            return -EINVAL;
-    if (ecd_ptr_device(loc) != device)
+    if (!scrub_on_device(device, ls.in, list->columns, ls.check, ls.nr, NULL, 0, loc, NULL))
         return -EINVAL;
     if (two ? !ecd_repair2 : !ecd_repair)
         return -ENODEV;
@@ -3911,20 +3874,14 @@ repair_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripe
     /* the tables of locate2: G, the heal matrix of the check bricks from the
      * k lowest bricks, and the pair inverses; the kernel rebuilds any named
      * set from them, so there is no row per pair */
-    rc = locate_args(list, avail_mask, (const void *const *)frags, loc, &ls);
-    if (rc == 0)
-        rc = locate_tables(list, &ls, &d, ratio);
+    rc = locate_tables(list, &ls, nstripes, &d, ratio);
     if (rc == 0)
         rc = locate2_tables(d.k, ls.nr, d.pat + d.k, ratio1, pinv);
+    G = d.pat + d.k;
+    if (rc == 0)
+        rc = gf_inv_row(G, 2 * d.k, ginv);
     if (rc)
         return rc;
-    G = d.pat + d.k;
-    for (i = 0; i < 2 * d.k; i++) {
-        v = ec_method_gf_div(1, G[i]);
-        if (v == 0 || v >= EC_GF_SIZE)
-            return -EINVAL;
-        ginv[i] = (uint8_t)v;
-    }
     return ecd_repair2(device, stream, d.k, nstripes, frags, (uint32_t)avail_mask, ls.nr, G, ginv,
                        pinv, loc);
 }
@@ -4030,17 +3987,6 @@ ecm_writev_encode_device_impl(ec_matrix_list_t *list, int device, void *stream, 
 
 /* ---------------------------------------------------- device-resident */
 
-static void
-desc_init(ecd_combine_desc_t *d, uint32_t k, uint32_t rows, uint64_t nstripes)
-{
-    memset(d, 0, offsetof(ecd_combine_desc_t, pat));
-    d->k = k;
-    d->rows = rows;
-    d->nstripes = nstripes;
-    d->npatterns = 1;
-    d->pat_bytes = k + rows * k;
-}
-
 static int32_t
 ecm_encode_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
                       const void *in, void *const *out)
@@ -4055,9 +4001,8 @@ ecm_encode_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_
         return 0;
     if (ecd_has_vander(ctx->k, ctx->n))
         return ecd_encode_vander(device, stream, ctx->k, ctx->n, nstripes, in, out);
-    desc_init(&d, ctx->k, ctx->n, nstripes);
-    d.in_stride = (uint64_t)ctx->k * EC_METHOD_CHUNK_SIZE;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    desc_init(&d, ctx->k, ctx->n, nstripes, (uint64_t)ctx->k * EC_METHOD_CHUNK_SIZE,
+              EC_METHOD_CHUNK_SIZE);
     for (p = 0; p < ctx->k; p++)
         d.in_base[p] = (const uint8_t *)in + (uint64_t)p * EC_METHOD_CHUNK_SIZE;
     for (p = 0; p < ctx->n; p++)
@@ -4086,9 +4031,7 @@ ecm_decode_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_
     m = matrix_get(list, mask, rows);
     if (!m)
         return -ENOMEM;
-    desc_init(&d, k, k, nstripes);
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = (uint64_t)k * EC_METHOD_CHUNK_SIZE;
+    desc_init(&d, k, k, nstripes, EC_METHOD_CHUNK_SIZE, (uint64_t)k * EC_METHOD_CHUNK_SIZE);
     for (p = 0; p < k; p++) {
         d.in_base[p] = in[p];
         src[p] = (uint8_t)p;
@@ -4122,10 +4065,8 @@ ecm_decode_mixed_device_impl(ec_matrix_list_t *list, int device, void *stream,
         return -E2BIG;
     if (nstripes == 0)
         return 0;
-    desc_init(&d, k, k, nstripes);
+    desc_init(&d, k, k, nstripes, EC_METHOD_CHUNK_SIZE, (uint64_t)k * EC_METHOD_CHUNK_SIZE);
     d.npatterns = nmasks;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = (uint64_t)k * EC_METHOD_CHUNK_SIZE;
     for (u = 0; u < list->rows; u++)
         d.in_base[u] = frags[u];
     for (r = 0; r < k; r++)
@@ -4165,17 +4106,10 @@ ecm_heal_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t 
         return -EINVAL;
     if (nstripes == 0)
         return 0;
-    memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
     rc = heal_pattern(list, mask, rows, target_mask, d.pat, &nt);
     if (rc)
         return rc;
-    d.k = list->columns;
-    d.rows = nt;
-    d.nstripes = nstripes;
-    d.npatterns = 1;
-    d.pat_bytes = d.k + nt * d.k;
-    d.in_stride = EC_METHOD_CHUNK_SIZE;
-    d.out_stride = EC_METHOD_CHUNK_SIZE;
+    desc_init_frags(&d, list->columns, nt, nstripes);
     for (p = 0; p < d.k; p++)
         d.in_base[p] = in[p];
     for (p = 0; p < nt; p++)
