@@ -688,7 +688,10 @@ PatTableCache &pat_tables()
 int upload_table(hipStream_t s, const ecd_combine_desc_t *d, CombineArgs &a, u32 **tab,
                  PatTableCache::Ref &ref)
 {
-    const size_t nw = (size_t)a.pwords * a.npatterns;
+    /* one zero word behind the last pattern: the k > 8 kernel fetches a row's
+     * words rw + 1 ... rw + 3 by its compile-time K, so with kw = 3 (k = 9 ...
+     * 12) the last row of the last pattern reads one word past its end */
+    const size_t nw = (size_t)a.pwords * a.npatterns + 1;
     std::vector<u32> w(nw, 0u);
     pack_words(d, a.kw, a.pwords, w.data());
     const int rc = pat_tables().acquire(s, w, ref);

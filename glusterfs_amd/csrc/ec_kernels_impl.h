@@ -1304,7 +1304,13 @@ __global__ __launch_bounds__(NW * 64) void ec_combine(const CombineArgs a)
     for (u32 it = wave; it < items; it += NW) {
         const u32 r = it / IPT, s = (it % IPT) * SPI + cs;
         const uint8_t *col = lds + s * 64u + cc * (4u * CW);
-        /* the row's coefficients: up to 4 words, loaded once into SGPRs */
+        /* the row's coefficients: up to 4 words, loaded once into SGPRs.
+         * Fetched by the compile-time K, not by kw: with K = 16 and kw = 3
+         * (k = 9 ... 12) w3 is the word behind the row -- the next row's
+         * first, the next pattern's src[], or the zero word upload_table
+         * puts behind a device table (the argument segment cannot end there:
+         * no such pwords divides 512).  Its bytes are never used: the loop
+         * below ends at p < k, before the shift register reaches them. */
         const u32 rw = a.kw * (1 + r);
         const u32 w0 = pw.word(a, rw);
         const u32 w1 = K > 4 ? pw.word(a, rw + 1) : 0u;
@@ -1404,6 +1410,9 @@ __global__ __launch_bounds__(NW * 64) void ec_combine_n(const CombineArgs a)
         for (int q = 0; q < RB; ++q) {
             const u32 rq = r + q;
             const bool has = q == 0 || rq < a.rows;     /* wave-uniform */
+            /* words by the compile-time K, as in ec_combine: here K <= 8 and
+             * kw = ceil(k / 4) is 2 wherever K = 8 runs (k = 5 ... 8), so
+             * no word past the row is fetched */
             const u32 rw = a.kw * (1 + (has ? rq : r));
             const u32 w0 = has ? pw.word(a, rw) : 0u;
             const u32 w1 = K > 4 && has ? pw.word(a, rw + 1) : 0u;

@@ -3,6 +3,14 @@
 Bit-exact comparison (integer GF(2^8) work: no tolerance).  Small seeded
 inputs go through both the oracle and the library; inputs are host numpy
 buffers (PCIe path) or torch device tensors (device-resident path).
+
+These are hand-picked geometries, most with the run-time k at the top of its
+K bucket (4, 8, 16).  The sweep of the device-resident combine over every k
+from 1 to 16, every row count and every launch branch (single pattern,
+tile-mixed, sorted slots, device table, non-temporal staging, the 4-wave
+kernels above 2^17 stripes) is tests/test_gpu_combine_sweep.py, on the case
+table of tests/_combine_sweep.py; tests/test_combine_sweep.py runs that table
+on the CPU engine.
 """
 import itertools
 
