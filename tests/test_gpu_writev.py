@@ -4,9 +4,15 @@ reference's read-modify-write (oracle.writev_merge: ec-inode-write.c:
 1825-1908, 1987-2085) followed by the oracle encode.  Bit-exact.
 
 Host buffers merge in the staging copy; device buffers go through the
-fused kernel (edge stripes gathered, interior read in place with
-realigned loads) or, for geometries without a compile-time encoder, a
-device-side gather + the generic encoder."""
+fused kernel (edge stripes gathered by ec_rmw_gather, interior read in place)
+or, for geometries without a compile-time encoder, a device-side gather + the
+generic encoder.  Today the interior is realigned in two places: the tile
+encoders of 4+2, 8+4 and 16+4 stage a byte-misaligned interior from
+dword-aligned loads shifted through registers (stage_tile_shift, SM = 3; a
+dword-aligned one by LDS-DMA at the caller's address, SM = 1), and the
+register kernels -- 2+1 always, the others under EC_MI355X_ENC=0 -- load
+dword-aligned and funnel-shift (ec_encode_vander_rmw<..., LM = 1>,
+load_plane_realign).  tests/test_gpu_encode_sweep.py sweeps both."""
 import numpy as np
 import pytest
 
