@@ -142,6 +142,18 @@ int ecd_decode_checked2(int device, void *stream, const ecd_combine_desc_t *d,
                         const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *ratio1,
                         const uint8_t *pair_inv, const uint8_t *inv, const uint8_t *ginv,
                         void *out, uint32_t *loc);
+/* A heal that corrects up to two chunks (ec_method_heal_checked2_device): the
+ * arguments of ecd_locate2 with basis_brick ascending, then ntargets, heal
+ * and out as for ecd_heal_checked and ginv as for ecd_decode_checked2.  The k
+ * + d->rows inputs and the m targets are different bricks of at most 31.
+ * loc[t] is ecd_locate2's.  Chunk t of out[j] gets row j applied to stripe t's
+ * k inputs, after the one or two inputs loc[t] names, if any, have been
+ * corrected to agree with the bricks it does not name. */
+int ecd_heal_checked2(int device, void *stream, const ecd_combine_desc_t *d,
+                      const void *const *check, const uint8_t *check_brick,
+                      const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *ratio1,
+                      const uint8_t *pair_inv, uint32_t ntargets, const uint8_t *heal,
+                      const uint8_t *ginv, void *const *out, uint32_t *loc);
 /* Repairing what locate named (ec_method_repair_device): frags[] is indexed
  * by brick and read for the bits of avail (no bit at or above 31); bset is
  * the k + 1 lowest bricks of avail, ascending: the basis B of ecd_locate and

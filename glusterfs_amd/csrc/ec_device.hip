@@ -1705,6 +1705,18 @@ int ecd_decode_checked2(int device, void *stream, const ecd_combine_desc_t *d,
     });
 }
 
+int ecd_heal_checked2(int device, void *stream, const ecd_combine_desc_t *d,
+                      const void *const *check, const uint8_t *check_brick,
+                      const uint8_t *basis_brick, const uint8_t *ratio, const uint8_t *ratio1,
+                      const uint8_t *pair_inv, uint32_t ntargets, const uint8_t *heal,
+                      const uint8_t *ginv, void *const *out, uint32_t *loc)
+{
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_heal_checked2(s, d, check, check_brick, basis_brick, ratio, ratio1, pair_inv,
+                                  ntargets, heal, ginv, out, loc);
+    });
+}
+
 int ecd_repair(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
                uint32_t avail, const uint8_t *bset, const uint8_t *coef, const uint32_t *loc)
 {

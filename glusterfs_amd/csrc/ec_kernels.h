@@ -53,6 +53,13 @@ int ecdk_decode_checked2(hipStream_t s, const ecd_combine_desc_t *d, const void 
                          const uint8_t *check_brick, const uint8_t *basis_brick,
                          const uint8_t *ratio, const uint8_t *ratio1, const uint8_t *pair_inv,
                          const uint8_t *inv, const uint8_t *ginv, void *out, uint32_t *loc);
+/* the heal corrected around up to two chunks of ecd_heal_checked2
+ * (ec_heal_checked2_n) */
+int ecdk_heal_checked2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                       const uint8_t *check_brick, const uint8_t *basis_brick,
+                       const uint8_t *ratio, const uint8_t *ratio1, const uint8_t *pair_inv,
+                       uint32_t ntargets, const uint8_t *heal, const uint8_t *ginv,
+                       void *const *out, uint32_t *loc);
 /* rewriting the chunks loc[] names, of ecd_repair (ec_repair_n) */
 int ecdk_repair(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
                 const uint8_t *bset, const uint8_t *coef, const uint32_t *loc);

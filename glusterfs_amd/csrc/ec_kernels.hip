@@ -14,7 +14,7 @@
  *            8-stripe ec_combine, 16 waves (two blocks fill a CU's 32 wave
  *            slots); both stage by LDS-DMA into a plane-major tile and
  *            multiply by a jump into the searched XOR programs
- *   scrub    six kernels on one narrow tile, the check fragments staged
+ *   scrub    seven kernels on one narrow tile, the check fragments staged
  *            beside the basis, put together from phases that are each
  *            written once (ec_kernels_impl.h) and launched by one launcher
  *            (launch_scrub_tile):
@@ -31,6 +31,9 @@
  *            chunks in LDS, one dense decode
  *   checked  a heal that checks its sources: ec_heal_checked_n, the checked
  *   heal     decode with the targets' heal matrix for inv(B), a row per target
+ *   checked2 the same heal around up to two chunks: ec_heal_checked2_n, the
+ *   heal     checked2 decode with the heal matrix, the target pointers in the
+ *            tail of the input list
  *   verified a read and a heal that only detect, from k + 1 fragments:
  *            ec_decode_verified_n and ec_heal_verified_n on the same tile,
  *            the check rows and the output rows in one loop (scrub_verified)
@@ -907,7 +910,7 @@ struct ScrubCfg {
     static constexpr int K = K_, NW = NW_, LA = LA_;
 };
 
-/* The launch of a four-stripe scrub tile kernel, for all six of them.
+/* The launch of a four-stripe scrub tile kernel, for all of them.
  * kernel(ScrubCfg<K, NW, LA>{}) gives the instantiation to run on the packed
  * arguments a; k, rows and nstripes are the geometry in a, align the OR of
  * its input addresses, nf the kernel's words per stripe, and a failed launch
@@ -1331,6 +1334,57 @@ int ecdk_decode_checked2(hipStream_t s, const ecd_combine_desc_t *d, const void 
                              [](auto c) {
         using C = decltype(c);
         return &ec_decode_checked2_n<C::K, C::NW, C::LA>;
+    });
+}
+
+/* ------------------------------------- a heal that corrects up to two chunks */
+
+/* As ecdk_locate2, then ntargets: the m targets; heal: m x k bytes, the heal
+ * matrix of the targets from the basis (row j gives the chunk of target j);
+ * ginv: 2 x k bytes, 1 / coefficient of row 0, then of row 1; out: the m
+ * target fragments, nstripes * 512 device bytes each at any alignment.  Every
+ * table travels in the kernel arguments: nothing is uploaded.  The target
+ * pointers take the slots of the input list behind the k + rows inputs
+ * (HealChecked2Args): a geometry whose inputs and targets are not different
+ * bricks of at most 31 does not fit and is -EINVAL. */
+int ecdk_heal_checked2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
+                       const uint8_t *check_brick, const uint8_t *basis_brick,
+                       const uint8_t *ratio, const uint8_t *ratio1, const uint8_t *pair_inv,
+                       uint32_t ntargets, const uint8_t *heal, const uint8_t *ginv,
+                       void *const *out, uint32_t *loc)
+{
+    static_assert(sizeof(HealChecked2Args) <= 2048, "the tables must fit the kernel arguments");
+    HealChecked2Args a;
+    uintptr_t o = 0;
+    if (!heal || !ginv || !out || ntargets == 0)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    if (int rc = pack_locate2(d, check, check_brick, basis_brick, ratio, ratio1, pair_inv, loc,
+                              a.l2, &o))
+        return rc;
+    LocateArgs &l = a.l2.l;
+    const u32 k = l.k, kw = l.kw, ni = k + l.rows;
+    if (ni + ntargets >= ECD_MAX_ROWS || kw * ntargets > kLocateWords)
+        return -EINVAL;
+    a.m = ntargets;
+    for (u32 j = 0; j < ntargets; ++j) {
+        if (!out[j])
+            return -EINVAL;
+        l.in[ni + j] = static_cast<const uint8_t *>(out[j]);
+        for (u32 p = 0; p < k; ++p)
+            a.heal[j * kw + (p >> 2)] |= (u32)heal[j * k + p] << ((p & 3u) * 8u);
+    }
+    for (u32 p = 0; p < k; ++p) {
+        if (ginv[p] == 0 || ginv[k + p] == 0)
+            return -EINVAL;
+        a.bmask |= 1u << basis_brick[p];
+        a.ginv[p >> 2] |= (u32)ginv[p] << ((p & 3u) * 8u);
+        a.ginv[ECD_MAX_K / 4 + (p >> 2)] |= (u32)ginv[k + p] << ((p & 3u) * 8u);
+    }
+    return launch_scrub_tile(s, a, k, l.rows, l.nstripes, o, 3, "launch_heal_checked2",
+                             [](auto c) {
+        using C = decltype(c);
+        return &ec_heal_checked2_n<C::K, C::NW, C::LA>;
     });
 }
 

@@ -1604,9 +1604,25 @@ struct DecodeChecked2Args {
     u32 ginv[2 * (ECD_MAX_K / 4)];
 };
 
+/* Kernel arguments of ec_heal_checked2_n: Locate2Args, then B as a brick mask,
+ * the number m of targets, T = the heal matrix of the targets from B laid out
+ * like the coefficients (row j at word j * kw) and the two ginv rows of
+ * DecodeChecked2Args.  The m target fragments (chunk t of target j at its
+ * pointer + t * 512, any byte alignment) have no list of their own: the a = k
+ * + rows inputs and the m targets are different bricks of at most 31, so a + m
+ * <= 31 and the targets stand behind the inputs, in l2.l.in[a .. a + m).  A
+ * separate list of 32 pointers would make 2,264 bytes; this is 2,008.  With a
+ * >= k + 4, m <= 27 - k and m * kw <= 56 words (k = 13): kLocateWords. */
+struct HealChecked2Args {
+    Locate2Args l2;
+    u32 bmask, m;
+    u32 heal[kLocateWords];
+    u32 ginv[2 * (ECD_MAX_K / 4)];
+};
+
 /* ------------------------------------------ scrub: the phases, once each */
 
-/* The tile kernels below (six, and the two detect-only ones after them) share
+/* The tile kernels below (seven, and the two detect-only ones after them) share
  * the narrow combine's shape: T = 4 stripes per block, 16 lanes per chunk,
  * one dword column of all 8 planes per lane,
  * with the check fragments staged beside the basis.  The tile is (k + rows) *
@@ -1990,6 +2006,56 @@ __device__ __forceinline__ void scrub_correct(const ScrubTile &t, u32 k, u32 bma
     }
 }
 
+/* The correction of up to two basis chunks, after the barrier of the last
+ * locate2 phase that ran, for a stripe whose final word W names one or two
+ * basis positions (the a - |S| other chunks lie on one codeword; its basis
+ * part is the stored basis with an error XORed into each named position):
+ *   p alone, or p and a check row c   e_p = s_ref / G[ref][p], ref = 0, or 1
+ *                                     when c is row 0 (rows >= 4: row 1 is
+ *                                     intact then);
+ *   p < q                             e_p = a s_0 ^ b s_1, e_q = c s_0 ^ d s_1,
+ *                                     {a, b, c, d} = pinv of the pair.
+ * That is at most four terms (coefficient, s_0 or s_1, slot), one loop around
+ * one multiply site, the tile's four stripes one per wave item as in
+ * scrub_correct: stripe s on lanes 16 s .. 16 s + 15 of one wave, its words
+ * final.  W names nb bricks of B: none (clean, check bricks only, MANY, past
+ * nstripes) leaves the stripe alone; one is position p, with s_0, or with s_1
+ * when W's other bit is the brick of check row 0; two are p < q with the four
+ * bytes of their pinv.  ginv: the k bytes 1 / G[0][p], and from word
+ * ECD_MAX_K / 4 on 1 / G[1][p]; bmask: B as a brick mask. */
+template <int NW>
+__device__ __forceinline__ void scrub_correct2(const ScrubTile &t, const Locate2Args &a,
+                                               u32 bmask, const u32 *ginv)
+{
+    const u32 k = a.l.k;
+    const uint8_t *syn = t.col + k * kScrubSlot;
+    for (u32 s = t.wave; s < kScrubT; s += NW) {
+        const u32 w = __builtin_amdgcn_readfirstlane(
+            locate2_word(t.flags[s], t.flags[kScrubT + s], t.flags[2 * kScrubT + s]));
+        const u32 wb = w & bmask;
+        if (wb == 0)
+            continue;
+        const bool two = (wb & (wb - 1u)) != 0;
+        const u32 p = (u32)__builtin_popcount(bmask & ((wb & (0u - wb)) - 1u));
+        const u32 q = (u32)__builtin_popcount(bmask & ((wb & (wb - 1u)) - 1u));
+        const u32 ref = !two && (w ^ wb) == 1u << packed_byte(a.l.cbrick, 0) ? 1u : 0u;
+        const u32 cw = two ? a.pinv[p * (2u * k - p - 1u) / 2u + q - p - 1u]
+                           : packed_byte(ginv + ref * (ECD_MAX_K / 4), p);
+        const u32 nterms = two ? 4u : 1u;
+#pragma unroll 1
+        for (u32 i = 0; i < nterms; ++i) {
+            const u32 c = __builtin_amdgcn_readfirstlane((cw >> (i * 8u)) & 0xFFu);
+            if (c == 0)
+                continue;
+            u32 acc[8][1] = {}, y[8][1];
+            read_column(syn + (two ? i & 1u : ref) * kScrubSlot, y);
+            ecgf::mul_xor_jt<1>(c, acc, y);
+            if (t.cs == s)
+                xor_column(t.col + (i < 2u ? p : q) * kScrubSlot, acc);
+        }
+    }
+}
+
 /* The decode of the tile's (corrected) basis slots: the k output rows are
  * spread over the waves like the check rows of phase 1; row j is the sum of
  * inv(B)[j][p] * x_p over the basis slots and leaves by dword stores, 64
@@ -2025,7 +2091,7 @@ __device__ __forceinline__ void scrub_heal(const ScrubTile &t, const u32 *heal, 
     }
 }
 
-/* ---------------------------------------------- scrub: the six tile kernels */
+/* ---------------------------------------------- scrub: the seven tile kernels */
 
 /* ec_method_verify_device: do the stored fragments of `rows` bricks agree
  * with what the k basis fragments imply?  Phase 1 alone, with one word per
@@ -2156,19 +2222,8 @@ __global__ __launch_bounds__(NW * 64) void ec_heal_checked_n(const HealCheckedAr
  * two early returns are ifs here: a clean tile skips phases 2 and 3 and the
  * correction, a tile without an open stripe skips phase 3.
  *
- * The correction, for a stripe whose final word W names one or two basis
- * positions (the a - |S| other chunks lie on one codeword; its basis part is
- * the stored basis with an error XORed into each named position):
- *   p alone, or p and a check row c   e_p = s_ref / G[ref][p], ref = 0, or 1
- *                                     when c is row 0 (rows >= 4: row 1 is
- *                                     intact then);
- *   p < q                             e_p = a s_0 ^ b s_1, e_q = c s_0 ^ d s_1,
- *                                     {a, b, c, d} = pinv of the pair.
- * That is at most four terms (coefficient, s_0 or s_1, slot), one loop around
- * one multiply site, the tile's four stripes one per wave item as in
- * ec_decode_checked_n.  MANY stripes, check-only stripes and stripes past
- * nstripes (W = 0) are left alone.  After it one dense decode with inv(B)
- * gives what inv(B_S) would give from the undamaged chunks. */
+ * After the correction (scrub_correct2) one dense decode with inv(B) gives
+ * what inv(B_S) would give from the undamaged chunks. */
 template <int K, int NW, int LA = kLdsDmaDefault>
 __global__ __launch_bounds__(NW * 64) void ec_decode_checked2_n(const DecodeChecked2Args a)
 {
@@ -2188,40 +2243,47 @@ __global__ __launch_bounds__(NW * 64) void ec_decode_checked2_n(const DecodeChec
             scrub_pairs<NW>(t, a.l2);
             __syncthreads();
         }
-        /* stripe s of the tile, on lanes 16 s .. 16 s + 15 of one wave: its
-         * words are final.  W names nb bricks of B: none (clean, check bricks
-         * only, MANY, past nstripes) leaves the stripe alone; one is position
-         * p, with s_0, or with s_1 when W's other bit is the brick of check
-         * row 0; two are p < q with the four bytes of their pinv. */
-        const uint8_t *syn = t.col + k * kScrubSlot;
-        for (u32 s = t.wave; s < kScrubT; s += NW) {
-            const u32 w = __builtin_amdgcn_readfirstlane(
-                locate2_word(t.flags[s], t.flags[kScrubT + s], t.flags[2 * kScrubT + s]));
-            const u32 wb = w & a.bmask;
-            if (wb == 0)
-                continue;
-            const bool two = (wb & (wb - 1u)) != 0;
-            const u32 p = (u32)__builtin_popcount(a.bmask & ((wb & (0u - wb)) - 1u));
-            const u32 q = (u32)__builtin_popcount(a.bmask & ((wb & (wb - 1u)) - 1u));
-            const u32 ref = !two && (w ^ wb) == 1u << packed_byte(l.cbrick, 0) ? 1u : 0u;
-            const u32 cw = two ? a.l2.pinv[p * (2u * k - p - 1u) / 2u + q - p - 1u]
-                               : packed_byte(a.ginv + ref * (ECD_MAX_K / 4), p);
-            const u32 nterms = two ? 4u : 1u;
-#pragma unroll 1
-            for (u32 i = 0; i < nterms; ++i) {
-                const u32 c = __builtin_amdgcn_readfirstlane((cw >> (i * 8u)) & 0xFFu);
-                if (c == 0)
-                    continue;
-                u32 acc[8][1] = {}, y[8][1];
-                read_column(syn + (two ? i & 1u : ref) * kScrubSlot, y);
-                ecgf::mul_xor_jt<1>(c, acc, y);
-                if (t.cs == s)
-                    xor_column(t.col + (i < 2u ? p : q) * kScrubSlot, acc);
-            }
-        }
+        scrub_correct2<NW>(t, a.l2, a.bmask, a.ginv);
         __syncthreads();
     }
     scrub_decode<K, NW>(t, a.inv, k, l.kw, a.out);
+    scrub_store_loc<3>(t, l);
+}
+
+/* ec_method_heal_checked2_device: regenerate the fragments of the target
+ * bricks from the k lowest bricks at hand and, in the same pass, check those
+ * against the others and correct up to two bad chunks: ec_decode_checked2_n
+ * with the heal matrix T = E_target * inv(B) in the place of inv(B) and one
+ * output per target, as ec_heal_checked_n is to ec_decode_checked_n.  T does
+ * not depend on the stripe: after the correction the basis chunks of a stripe
+ * that names the set S lie on the codeword of the other a - |S| chunks, and T
+ * applied to them is what the heal matrix of B_S gives from the undamaged
+ * ones.  MANY stripes are healed from B as stored.  The targets are the m
+ * pointers behind the inputs (HealChecked2Args); scrub_stage reads only the
+ * first k + rows. */
+template <int K, int NW, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_heal_checked2_n(const HealChecked2Args a)
+{
+    static_assert(NW >= (int)kScrubT, "a wave per stripe of the tile");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const LocateArgs &l = a.l2.l;
+    const u32 k = l.k, kw = l.kw, rows = l.rows;
+    ScrubTile t = scrub_stage<3, NW, LA>(lds, l);
+    __syncthreads();
+    scrub_place(t, lds, l.nstripes);
+    scrub_syndromes<K, NW, true>(t, l.coef, l.cbrick, k, kw, rows);
+    __syncthreads();
+    if (scrub_dirty(t)) {
+        scrub_single<NW>(t, l);
+        __syncthreads();
+        if (scrub_wants_pairs(t)) {
+            scrub_pairs<NW>(t, a.l2);
+            __syncthreads();
+        }
+        scrub_correct2<NW>(t, a.l2, a.bmask, a.ginv);
+        __syncthreads();
+    }
+    scrub_heal<K, NW>(t, a.heal, k, kw, a.m, const_cast<uint8_t *const *>(l.in + k + rows));
     scrub_store_loc<3>(t, l);
 }
 

@@ -3432,16 +3432,18 @@ decode_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t
 
 /* ------------------------------------------- a heal that checks its sources */
 
-/* Weak like ecd_locate: without the symbol ec_method_heal_checked_device is
- * -ENODEV. */
+/* Weak like ecd_locate: without the symbols ec_method_heal_checked_device and
+ * ec_method_heal_checked2_device are -ENODEV. */
 extern __typeof__(ecd_heal_checked) ecd_heal_checked __attribute__((weak));
+extern __typeof__(ecd_heal_checked2) ecd_heal_checked2 __attribute__((weak));
 
-/* The host call.  The stripes are healed in runs that share a mask, as
- * decode_checked_host decodes them; loc[] is ec_method_locate's. */
+/* Both host calls: `two` = ec_method_heal_checked2 (a >= k + 4, loc[] is
+ * ec_method_locate2's and a pair is healed around).  The stripes are healed
+ * in runs that share a mask, as decode_checked_host decodes them. */
 static int32_t
 heal_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
                   const void *const *frags, uintptr_t target_mask, void *const *out,
-                  uint32_t *loc, uint64_t *nbad, uint64_t *nmany)
+                  uint32_t *loc, uint64_t *nbad, uint64_t *nmany, int two)
 {
     ecm_locate_sets_t s;
     ecm_mask_run_t run = {0};
@@ -3450,7 +3452,7 @@ heal_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mas
     uint32_t rows[ECM_MAX_K], nt = 0, n, b, p, j;
     int rc;
 
-    rc = avail_sets(list, avail_mask, frags, loc, 2, &s);
+    rc = avail_sets(list, avail_mask, frags, loc, two ? 4 : 2, &s);
     if (rc)
         return rc;
     if (!heal_targets_ok(list, avail_mask, target_mask, out, &nt))
@@ -3460,7 +3462,7 @@ heal_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mas
     /* locate_host looks at the fragments and loc before it writes */
     if (!scrub_on_host(NULL, 0, NULL, 0, out, nt, NULL, NULL))
         return -EINVAL;
-    rc = locate_host(list, nstripes, avail_mask, frags, loc, &bad, 0);
+    rc = locate_host(list, nstripes, avail_mask, frags, loc, &bad, two);
     if (rc)
         return rc;
     desc_init_frags(&d, list->columns, nt, 0);
@@ -3491,21 +3493,23 @@ heal_checked_host(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mas
     return 0;
 }
 
-/* The device call: locate's tables, T = the heal matrix of the targets from
- * B, and 1 / G[0][p] for the correction. */
+/* Both device calls: `two` = ec_method_heal_checked2_device.  locate's
+ * tables (with `two` locate2's as well), T = the heal matrix of the targets
+ * from B, and 1 / G[0][p] for the correction. */
 static int32_t
 heal_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
                     uintptr_t avail_mask, const void *const *frags, uintptr_t target_mask,
-                    void *const *out, uint32_t *loc)
+                    void *const *out, uint32_t *loc, int two)
 {
     ecm_locate_sets_t s;
     ecd_combine_desc_t d;
-    uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ginv[ECM_MAX_K];
+    uint8_t ratio[ECM_MAX_N * ECM_MAX_K], ratio1[ECM_MAX_N * ECM_MAX_K], ginv[2 * ECM_MAX_K];
+    uint8_t pinv[ECM_MAX_K * (ECM_MAX_K - 1) / 2 * 4];
     uint8_t pat[ECM_MAX_K + ECM_MAX_N * ECM_MAX_K];
     uint32_t nt = 0, n;
     int rc;
 
-    rc = avail_sets(list, avail_mask, frags, loc, 2, &s);
+    rc = avail_sets(list, avail_mask, frags, loc, two ? 4 : 2, &s);
     if (rc)
         return rc;
     if (!heal_targets_ok(list, avail_mask, target_mask, out, &nt))
@@ -3514,19 +3518,25 @@ heal_checked_device(ec_matrix_list_t *list, int device, void *stream, uint64_t n
         return 0;
     if (!scrub_on_device(device, s.in, list->columns, s.check, s.nr, out, nt, loc, NULL))
         return -EINVAL;
-    if (!ecd_heal_checked)
+    if (two ? !ecd_heal_checked2 : !ecd_heal_checked)
         return -ENODEV;
     rc = locate_tables(list, &s, nstripes, &d, ratio);
+    if (rc == 0 && two)
+        rc = locate2_tables(d.k, s.nr, d.pat + d.k, ratio1, pinv);
     if (rc == 0)
         rc = heal_pattern(list, s.bmask, s.rows, target_mask, pat, &n);
     if (rc)
         return rc;
     if (n != nt)
         return -EINVAL;
-    /* 1 / G[0][p]: the error of basis position p from the first syndrome */
-    rc = gf_inv_row(d.pat + d.k, d.k, ginv);
+    /* 1 / G[0][p]: the error of basis position p from the first syndrome;
+     * with `two` also 1 / G[1][p], for a pair whose check brick is row 0 */
+    rc = gf_inv_row(d.pat + d.k, (two ? 2 : 1) * d.k, ginv);
     if (rc)
         return rc;
+    if (two)
+        return ecd_heal_checked2(device, stream, &d, s.check, s.cb, s.bb, ratio, ratio1, pinv, nt,
+                                 pat + d.k, ginv, out, loc);
     return ecd_heal_checked(device, stream, &d, s.check, s.cb, s.bb, ratio, nt, pat + d.k, ginv,
                             out, loc);
 }
@@ -4305,7 +4315,7 @@ ec_method_heal_checked(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avai
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_heal_checked", seq,
                    heal_checked_host(list, nstripes, avail_mask, frags, target_mask, out, loc,
-                                     nbad, nmany));
+                                     nbad, nmany, 0));
 }
 
 int32_t
@@ -4317,7 +4327,30 @@ ec_method_heal_checked_device(ec_matrix_list_t *list, int device, void *stream,
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_heal_checked_device", seq,
                    heal_checked_device(list, device, stream, nstripes, avail_mask, frags,
-                                       target_mask, out, loc));
+                                       target_mask, out, loc, 0));
+}
+
+int32_t
+ec_method_heal_checked2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                        const void *const *frags, uintptr_t target_mask, void *const *out,
+                        uint32_t *loc, uint64_t *nbad, uint64_t *nmany)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_checked2", seq,
+                   heal_checked_host(list, nstripes, avail_mask, frags, target_mask, out, loc,
+                                     nbad, nmany, 1));
+}
+
+int32_t
+ec_method_heal_checked2_device(ec_matrix_list_t *list, int device, void *stream,
+                               uint64_t nstripes, uintptr_t avail_mask,
+                               const void *const *frags, uintptr_t target_mask,
+                               void *const *out, uint32_t *loc)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_checked2_device", seq,
+                   heal_checked_device(list, device, stream, nstripes, avail_mask, frags,
+                                       target_mask, out, loc, 1));
 }
 
 int32_t

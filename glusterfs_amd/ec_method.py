@@ -60,6 +60,7 @@ EXPORTS = (
     "ec_method_decode_checked", "ec_method_decode_checked_device",
     "ec_method_decode_checked2", "ec_method_decode_checked2_device",
     "ec_method_heal_checked", "ec_method_heal_checked_device",
+    "ec_method_heal_checked2", "ec_method_heal_checked2_device",
     "ec_method_decode_verified", "ec_method_decode_verified_device",
     "ec_method_heal_verified", "ec_method_heal_verified_device",
 )
@@ -180,6 +181,9 @@ def _load():
         "ec_method_heal_checked": (i32, [P, u64, up, vp, up, vp, vp, ctypes.POINTER(u64),
                                          ctypes.POINTER(u64)]),
         "ec_method_heal_checked_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
+        "ec_method_heal_checked2": (i32, [P, u64, up, vp, up, vp, vp, ctypes.POINTER(u64),
+                                          ctypes.POINTER(u64)]),
+        "ec_method_heal_checked2_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, up, vp, vp]),
         "ec_method_decode_verified": (i32, [P, u64, up, vp, vp, vp, ctypes.POINTER(u64)]),
         "ec_method_decode_verified_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp, vp]),
         "ec_method_heal_verified": (i32, [P, u64, up, vp, up, vp, vp, ctypes.POINTER(u64)]),
@@ -655,6 +659,18 @@ class ECMatrixList:
                "ec_method_decode_checked2")
         return nbad.value, nmany.value
 
+    def heal_checked2(self, nstripes, avail_mask, frags, target_mask, out, loc):
+        """ec_method_heal_checked2: a heal that corrects two chunks.  As
+        heal_checked, with k + 4 bricks in avail_mask: `loc` gets locate2's
+        answer and every `out[j]` the heal around the one or two bricks it
+        names.  Returns (nbad, nmany)."""
+        nbad, nmany = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _check(lib.ec_method_heal_checked2(ctypes.byref(self._list), nstripes, avail_mask,
+                                           _ptr_array(frags), target_mask, _ptr_array(out),
+                                           addr(loc), ctypes.byref(nbad), ctypes.byref(nmany)),
+               "ec_method_heal_checked2")
+        return nbad.value, nmany.value
+
     def repair(self, nstripes, avail_mask, frags, loc):
         """ec_method_repair: where loc[t] is 1 << brick for a brick of
         avail_mask (k + 1 bricks are enough), rewrite chunk t of that brick's
@@ -769,6 +785,14 @@ class ECMatrixList:
         return _check(lib.ec_method_decode_checked2_device(
             ctypes.byref(self._list), device, stream, nstripes, avail_mask, _ptr_array(frags),
             addr(out), addr(loc)), "ec_method_decode_checked2_device")
+
+    def heal_checked2_device(self, device, stream, nstripes, avail_mask, frags, target_mask, out,
+                             loc):
+        """ec_method_heal_checked2_device: the same on device buffers (every
+        `out[j]` and `loc` too), queued on `stream`; nothing is counted."""
+        return _check(lib.ec_method_heal_checked2_device(
+            ctypes.byref(self._list), device, stream, nstripes, avail_mask, _ptr_array(frags),
+            target_mask, _ptr_array(out), addr(loc)), "ec_method_heal_checked2_device")
 
     def repair_device(self, device, stream, nstripes, avail_mask, frags, loc):
         """ec_method_repair_device: the same on device buffers (`loc` too),

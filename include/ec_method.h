@@ -356,6 +356,62 @@ int32_t ec_method_heal_checked_device(ec_matrix_list_t *list, int device, void *
                                       const void *const *frags, uintptr_t target_mask,
                                       void *const *out, uint32_t *loc);
 
+/* A heal that corrects two chunks: ec_method_heal and ec_method_locate2 in
+ * one pass over the fragments.  ec_method_heal_checked answers
+ * EC_MI355X_LOCATE_MANY for a stripe with two damaged source chunks and heals
+ * it from B as stored, which is wrong bytes in every target; with a >= k + 4
+ * fragments at hand such a stripe still has exactly one nearest codeword, and
+ * this call heals around the pair.  Everything is ec_method_heal_checked's --
+ * arguments, buffer rules, asynchrony, alignment (the device variant takes
+ * each out[j] at any byte alignment, loc wants 4), counters and error codes --
+ * except:
+ *
+ * avail_mask must name a >= k + 4 bricks, as for ec_method_locate2; fewer are
+ * -EINVAL.  A target beside k + 4 available bricks takes n - k >= 5, so every
+ * call on a 2+1, 4+2, 8+4 or 16+4 volume is -EINVAL.
+ *
+ * loc[t] is exactly what ec_method_locate2 gives on the same arguments, every
+ * loc[0..nstripes) written, each by one plain store.
+ *
+ * With B the k lowest bricks of avail_mask and B_S the k lowest bricks of
+ * avail_mask not in the set S, chunk t of every out[j] is, from the stored
+ * chunks, what ec_method_heal gives for that stripe with the same target_mask
+ * and
+ *   loc[t] == 0                      mask B;
+ *   loc[t] has the one or two bits   mask B_S.  For one bit this is
+ *   of S                             ec_method_heal_checked's answer, byte for
+ *                                    byte; for two check bricks B_S = B; for
+ *                                    basis + check and basis + basis the
+ *                                    damaged chunks are not used;
+ *   loc[t] == EC_MI355X_LOCATE_MANY  mask B as stored: defined bytes, but the
+ *                                    caller must treat the stripe as -EIO.
+ * So wherever at most two chunks of a stripe are damaged, every out[j] chunk
+ * is the chunk the original data encodes to, and wherever
+ * ec_method_heal_checked gives 0 or one bit both calls give the same loc[t]
+ * and the same target bytes.  The a - k == 4 caveat of ec_method_locate2
+ * carries over.  Nothing in frags is written, nothing past nstripes*512 of any
+ * out[j], and only the out[j] of target_mask.  nstripes == 0 returns 0 after
+ * the argument checks and writes nothing.
+ *
+ * The device variant can be followed on one stream, with no host
+ * synchronisation, by ec_method_repair2_device on the same loc and then
+ * ec_method_locate2_device: afterwards the sources are clean, the targets are
+ * right and the second locate2 is all zero.  It uploads nothing (locate2's
+ * tables, the heal matrix of the targets from B and the target pointers all
+ * travel in the kernel arguments), pre-zeroes nothing, uses no global atomics
+ * and counts nothing (-ENODEV where the device layer lacks it); the host
+ * variant runs on the calling thread's CPU engine whatever the volume's
+ * engine is and leaves ec_method_stats_t, the router and the run-time
+ * compiler alone. */
+int32_t ec_method_heal_checked2(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t avail_mask,
+                                const void *const *frags, uintptr_t target_mask,
+                                void *const *out, uint32_t *loc, uint64_t *nbad,
+                                uint64_t *nmany);
+int32_t ec_method_heal_checked2_device(ec_matrix_list_t *list, int device, void *stream,
+                                       uint64_t nstripes, uintptr_t avail_mask,
+                                       const void *const *frags, uintptr_t target_mask,
+                                       void *const *out, uint32_t *loc);
+
 /* A read and a heal that only detect, from k + 1 fragments.  The checked
  * calls above want a >= k + 2 fragments, which leaves out every 2+1 volume, a
  * 4+2 read with one brick down and the ordinary 4+2 heal (five sources, one
