@@ -24,6 +24,9 @@ from .ec_method import (  # noqa: F401
     inverse_matrix,
     mask_rows,
     pool_stats,
+    scrub_report,
+    scrub_report_device,
+    scrub_report_work,
     stats,
     sync_device,
 )

@@ -176,6 +176,28 @@ int ecd_repair(int device, void *stream, uint32_t k, uint64_t nstripes, void *co
 int ecd_repair2(int device, void *stream, uint32_t k, uint64_t nstripes, void *const *frags,
                 uint32_t avail, uint32_t rows, const uint8_t *g, const uint8_t *ginv,
                 const uint8_t *pair_inv, const uint32_t *loc);
+/* Summary and ordered compaction of a loc[] / bad[] array
+ * (ec_method_scrub_report_device): every buffer is device memory.  loc
+ * (nstripes dwords) is read only.  report gets the 34 words of
+ * ec_method_scrub_report_t: stripes with a non-zero word, those of them with
+ * bit 31, min(the first, cap), and per bit i < 31 the stripes that have it.
+ * idx[r] (may be NULL when cap == 0) gets the index of the r-th non-zero word
+ * in ascending order and val[r] (may be NULL) the word, for r < cap; nothing
+ * at or past min(count, cap) is written.  work is scratch of
+ * ECD_REPORT_WORK(nstripes) bytes, 8-byte aligned: per tile of
+ * ECD_REPORT_TILE stripes one 64-bit offset, then ECD_REPORT_COUNTERS planes
+ * of one dword per tile (non-zero words, bit 31, bits 0..30).  Three launches
+ * (two when cap == 0), no global atomics, no block waits on another.
+ * -EINVAL above ECD_REPORT_MAX_STRIPES. */
+#define ECD_REPORT_TILE 4096u
+#define ECD_REPORT_COUNTERS 33u
+#define ECD_REPORT_MAX_STRIPES ((uint64_t)1 << 40)
+#define ECD_REPORT_TILES(nstripes) \
+    ((uint64_t)(nstripes) / ECD_REPORT_TILE + ((uint64_t)(nstripes) % ECD_REPORT_TILE != 0))
+#define ECD_REPORT_WORK(nstripes) \
+    ((ECD_REPORT_TILES(nstripes) * (8u + 4u * ECD_REPORT_COUNTERS) + 7u) & ~(uint64_t)7u)
+int ecd_scrub_report(int device, void *stream, uint64_t nstripes, const uint32_t *loc,
+                     uint64_t *report, uint64_t cap, uint64_t *idx, uint32_t *val, void *work);
 int ecd_sync(int device, void *stream);
 
 /* ---- host-memory entry points: stripes are partitioned across `ndev`

@@ -1734,6 +1734,14 @@ int ecd_repair2(int device, void *stream, uint32_t k, uint64_t nstripes, void *c
     });
 }
 
+int ecd_scrub_report(int device, void *stream, uint64_t nstripes, const uint32_t *loc,
+                     uint64_t *report, uint64_t cap, uint64_t *idx, uint32_t *val, void *work)
+{
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_scrub_report(s, nstripes, loc, report, cap, idx, val, work);
+    });
+}
+
 int ecd_sync(int device, void *stream)
 {
     if (ecd_device_count() <= device || device < 0)

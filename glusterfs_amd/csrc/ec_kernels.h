@@ -67,6 +67,10 @@ int ecdk_repair(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags
 int ecdk_repair2(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frags, uint32_t avail,
                  uint32_t rows, const uint8_t *g, const uint8_t *ginv, const uint8_t *pair_inv,
                  const uint32_t *loc);
+/* the counts and the ordered list of the non-zero words of loc[], of
+ * ecd_scrub_report (ec_report_count, ec_report_scan, ec_report_scatter) */
+int ecdk_scrub_report(hipStream_t s, uint64_t nstripes, const uint32_t *loc, uint64_t *report,
+                      uint64_t cap, uint64_t *idx, uint32_t *val, void *work);
 /* Partial-stripe writes: materialise bytes [o0, o0+n) (n % 16 == 0) of the
  * virtual input {head[0:b1) | user[0:b2-b1) | tail[...]} into dst, and the
  * fused Vandermonde encode that reads interior stripes from user directly. */

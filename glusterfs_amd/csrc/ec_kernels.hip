@@ -1499,6 +1499,48 @@ int ecdk_repair2(hipStream_t s, uint32_t k, uint64_t nstripes, void *const *frag
     return launch_ok("launch_repair2");
 }
 
+/* loc: nstripes device dwords, read only; report: 34 device words; idx / val:
+ * cap entries each (idx may be NULL when cap == 0, val always); work:
+ * ECD_REPORT_WORK(nstripes) device bytes.  Count, scan and, when anything can
+ * be listed, scatter, back to back on s. */
+int ecdk_scrub_report(hipStream_t s, uint64_t nstripes, const uint32_t *loc, uint64_t *report,
+                      uint64_t cap, uint64_t *idx, uint32_t *val, void *work)
+{
+    ReportArgs a;
+    if (!loc || !report || ((uintptr_t)loc & 3u) || ((uintptr_t)val & 3u) ||
+        (((uintptr_t)report | (uintptr_t)idx | (uintptr_t)work) & 7u) || (cap > 0 && !idx) ||
+        nstripes > ECD_REPORT_MAX_STRIPES)
+        return -EINVAL;
+    if (nstripes == 0)
+        return 0;
+    if (!work)
+        return -EINVAL;
+    a.loc = loc;
+    a.nstripes = nstripes;
+    a.ntiles = ECD_REPORT_TILES(nstripes);
+    a.cap = cap;
+    a.off = static_cast<uint64_t *>(work);
+    a.part = reinterpret_cast<u32 *>(a.off + a.ntiles);
+    a.report = report;
+    a.idx = idx;
+    a.val = val;
+    /* a block per tile; a few blocks per CU stride over the rest */
+    uint64_t g = a.ntiles;
+    const uint64_t most = (uint64_t)cu_count() * 8u;
+    if (g > most)
+        g = most;
+    hipLaunchKernelGGL(ec_report_count, dim3((u32)g), dim3(kReportThreads), 0, s, a);
+    int rc = launch_ok("launch_report_count");
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(ec_report_scan, dim3(1), dim3(kReportThreads), 0, s, a);
+    rc = launch_ok("launch_report_scan");
+    if (rc || cap == 0)
+        return rc;
+    hipLaunchKernelGGL(ec_report_scatter, dim3((u32)g), dim3(kReportThreads), 0, s, a);
+    return launch_ok("launch_report_scatter");
+}
+
 /* Host-buffer combines with k <= 8 run the persistent double-buffered
  * ec_combine_zc_db (default since r04; EC_MI355X_ZCDB=0 keeps one tile per
  * block, ec_combine_zc, for A/B runs).  Pinned 8+4 / 4+2 decodes, same

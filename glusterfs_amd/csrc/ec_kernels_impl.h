@@ -2655,6 +2655,206 @@ __global__ __launch_bounds__(kRepairThreads) void ec_repair2_n(const Repair2Args
     }
 }
 
+/* ------------------------------------------- scrub: the report of loc[] */
+
+/* ec_method_scrub_report_device: what a scrubber acts on, from the loc[] or
+ * bad[] the calls above wrote: how many words are not zero, how many of those
+ * have bit 31, how many have each brick's bit, and the indices and values of
+ * the non-zero ones in ascending order, cut at cap.  Three launches on one
+ * stream, each block of 256 threads:
+ *   ec_report_count    per tile of ECD_REPORT_TILE stripes, the 33 partial
+ *                      counts, each by one plain store into its plane of work
+ *   ec_report_scan     one block: the exclusive offsets of the tiles and the
+ *                      report
+ *   ec_report_scatter  per tile with entries below cap, idx[] and val[]
+ * The grid of the first and the last is capped and strides over the tiles, so
+ * it is a legal launch whatever nstripes is.  A tile is 16 rounds of 256
+ * stripes, a dword per lane: stripe i * 256 + wave * 64 + lane of the tile is
+ * lane `lane` of wave `wave` in round i, so ascending (round, wave, lane) is
+ * ascending stripe order and a rank is the entries of earlier (round, wave)
+ * pairs plus the lower lanes of the ballot.  No global atomics; no block reads
+ * what another block of the same launch writes. */
+constexpr u32 kReportThreads = 256, kReportWaves = kReportThreads / 64;
+constexpr u32 kReportRounds = ECD_REPORT_TILE / kReportThreads;
+
+/* off and part are the two parts of work: ntiles 64-bit words, then
+ * ECD_REPORT_COUNTERS planes of ntiles dwords (plane 0: non-zero words, 1: bit
+ * 31, 2 + b: bit b). */
+struct ReportArgs {
+    const u32 *loc;
+    uint64_t nstripes, ntiles, cap;
+    uint64_t *off;
+    u32 *part;
+    uint64_t *report, *idx;
+    u32 *val;
+};
+
+/* this lane's 16 words of a tile, zero past the end of loc[] */
+__device__ __forceinline__ void report_load(const ReportArgs &a, uint64_t tile, u32 tid,
+                                            u32 (&v)[kReportRounds])
+{
+    const uint64_t t0 = tile * ECD_REPORT_TILE + tid;
+#pragma unroll
+    for (u32 i = 0; i < kReportRounds; ++i) {
+        const uint64_t t = t0 + i * kReportThreads;
+        v[i] = t < a.nstripes ? a.loc[t] : 0u;
+    }
+}
+
+/* inclusive scan of x over the 64 lanes of a wave */
+__device__ __forceinline__ u32 report_wave_scan(u32 x, u32 lane)
+{
+#pragma unroll
+    for (u32 o = 1; o < 64u; o <<= 1) {
+        const u32 y = __shfl_up(x, o);
+        if (lane >= o)
+            x += y;
+    }
+    return x;
+}
+
+/* A wave whose 64 words are all zero -- every wave of clean data -- pays the
+ * load and one ballot; the 32 ballots per bit run only behind a non-zero one.
+ * The counters are wave-uniform. */
+__global__ __launch_bounds__(kReportThreads) void ec_report_count(const ReportArgs a)
+{
+    __shared__ u32 wpart[kReportWaves][ECD_REPORT_COUNTERS];
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+        u32 v[kReportRounds], c[ECD_REPORT_COUNTERS];
+        report_load(a, tile, tid, v);
+#pragma unroll
+        for (u32 j = 0; j < ECD_REPORT_COUNTERS; ++j)
+            c[j] = 0;
+#pragma unroll
+        for (u32 i = 0; i < kReportRounds; ++i) {
+            const uint64_t dirty = __ballot(v[i] != 0);
+            if (dirty == 0)
+                continue;
+            c[0] += (u32)__popcll(dirty);
+            c[1] += (u32)__popcll(__ballot((v[i] >> 31) != 0));
+#pragma unroll
+            for (u32 b = 0; b < 31u; ++b)
+                c[2 + b] += (u32)__popcll(__ballot(((v[i] >> b) & 1u) != 0));
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (u32 j = 0; j < ECD_REPORT_COUNTERS; ++j)
+                wpart[wave][j] = c[j];
+        }
+        __syncthreads();
+        if (tid < ECD_REPORT_COUNTERS) {
+            u32 s = 0;
+#pragma unroll
+            for (u32 w = 0; w < kReportWaves; ++w)
+                s += wpart[w][tid];
+            a.part[(uint64_t)tid * a.ntiles + tile] = s;
+        }
+        __syncthreads();                /* wpart is the next tile's too */
+    }
+}
+
+/* One block walks the tiles 256 at a time, whatever their number: plane 0
+ * becomes the exclusive offsets in off[] (a round's sum is below 2^20, the
+ * running total is 64 bits), then each other plane is summed by the block.
+ * The report is 34 plain stores. */
+__global__ __launch_bounds__(kReportThreads) void ec_report_scan(const ReportArgs a)
+{
+    __shared__ u32 wsum[kReportWaves];
+    __shared__ uint64_t red[ECD_REPORT_COUNTERS - 1][kReportWaves];
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    uint64_t run = 0;
+    for (uint64_t base = 0; base < a.ntiles; base += kReportThreads) {
+        const uint64_t j = base + tid;
+        const u32 c = j < a.ntiles ? a.part[j] : 0u;
+        const u32 x = report_wave_scan(c, lane);
+        if (lane == 63u)
+            wsum[wave] = x;
+        __syncthreads();
+        u32 before = 0, total = 0;
+#pragma unroll
+        for (u32 w = 0; w < kReportWaves; ++w) {
+            const u32 s = wsum[w];
+            before += w < wave ? s : 0u;
+            total += s;
+        }
+        if (j < a.ntiles)
+            a.off[j] = run + before + (x - c);
+        run += total;
+        __syncthreads();                /* wsum is the next round's too */
+    }
+#pragma unroll 1
+    for (u32 k = 1; k < ECD_REPORT_COUNTERS; ++k) {
+        const u32 *p = a.part + (uint64_t)k * a.ntiles;
+        unsigned long long s = 0;
+        for (uint64_t j = tid; j < a.ntiles; j += kReportThreads)
+            s += p[j];
+#pragma unroll
+        for (u32 o = 32; o > 0; o >>= 1)
+            s += __shfl_down(s, o);
+        if (lane == 0)
+            red[k - 1][wave] = s;
+    }
+    __syncthreads();
+    /* ec_method_scrub_report_t: nbad, nmany, listed, brick[31] */
+    if (tid < ECD_REPORT_COUNTERS - 1u) {
+        uint64_t s = 0;
+#pragma unroll
+        for (u32 w = 0; w < kReportWaves; ++w)
+            s += red[tid][w];
+        a.report[tid == 0 ? 1u : tid + 2u] = s;
+    } else if (tid == ECD_REPORT_COUNTERS - 1u) {
+        a.report[0] = run;
+        a.report[2] = run < a.cap ? run : a.cap;
+    }
+}
+
+/* A tile with no entry, or whose first entry is at or past cap, costs its two
+ * words of work.  Any other recounts its 64 (round, wave) ballots into LDS,
+ * wave 0 scans them, and every non-zero lane below cap stores its entry. */
+__global__ __launch_bounds__(kReportThreads) void ec_report_scatter(const ReportArgs a)
+{
+    static_assert(kReportRounds * kReportWaves == 64, "wave 0 scans one count per lane");
+    __shared__ u32 pre[kReportRounds * kReportWaves];
+    const u32 tid = threadIdx.x, lane = tid & 63u;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (uint64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+        const u32 n = a.part[tile];
+        const uint64_t off = a.off[tile];
+        if (n == 0 || off >= a.cap)     /* the same for the whole block */
+            continue;
+        u32 v[kReportRounds];
+        report_load(a, tile, tid, v);
+#pragma unroll
+        for (u32 i = 0; i < kReportRounds; ++i) {
+            const uint64_t dirty = __ballot(v[i] != 0);
+            if (lane == 0)
+                pre[i * kReportWaves + wave] = (u32)__popcll(dirty);
+        }
+        __syncthreads();
+        if (wave == 0) {
+            const u32 c = pre[lane];
+            pre[lane] = report_wave_scan(c, lane) - c;
+        }
+        __syncthreads();
+#pragma unroll
+        for (u32 i = 0; i < kReportRounds; ++i) {
+            const uint64_t dirty = __ballot(v[i] != 0);
+            const u32 below = __builtin_amdgcn_mbcnt_hi(
+                (u32)(dirty >> 32), __builtin_amdgcn_mbcnt_lo((u32)dirty, 0u));
+            const uint64_t r = off + pre[i * kReportWaves + wave] + below;
+            if (v[i] != 0 && r < a.cap) {
+                a.idx[r] = tile * ECD_REPORT_TILE + i * kReportThreads + tid;
+                if (a.val)
+                    a.val[r] = v[i];
+            }
+        }
+        __syncthreads();                /* pre is the next tile's too */
+    }
+}
+
 /* Zero-copy variant for the host-buffer path, where every input and output
  * lives in pinned host memory and the CUs read and write it over PCIe
  * (ec_device.hip run_pipeline).  There the link, not HBM or the VALU, is the

@@ -3896,6 +3896,98 @@ repair_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripe
                        pinv, loc);
 }
 
+/* ------------------------------------------- the report of a scrub */
+
+/* Weak like ecd_repair: without the symbol ec_method_scrub_report_device is
+ * -ENODEV. */
+extern __typeof__(ecd_scrub_report) ecd_scrub_report __attribute__((weak));
+
+/* the device layer writes the report as 34 words */
+_Static_assert(sizeof(ec_method_scrub_report_t) == 272 &&
+               offsetof(ec_method_scrub_report_t, brick) == 24, "ec_method_scrub_report_t");
+
+/* What both entry points check first.  The call takes no list: loc[] may come
+ * from any volume. */
+static int
+report_args(const uint32_t *loc, const ec_method_scrub_report_t *report, uint64_t cap,
+            const uint64_t *idx, const uint32_t *val)
+{
+    if (!loc || !report || (cap > 0 && !idx))
+        return -EINVAL;
+    if ((((uintptr_t)loc | (uintptr_t)val) & 3u) || (((uintptr_t)report | (uintptr_t)idx) & 7u))
+        return -EINVAL;
+    return 0;
+}
+
+/* One walk over loc[] in stripe order: the device kernels count and rank in
+ * another order and must give these bytes. */
+static int32_t
+ecm_scrub_report_impl(uint64_t nstripes, const uint32_t *loc, ec_method_scrub_report_t *report,
+                      uint64_t cap, uint64_t *idx, uint32_t *val)
+{
+    ec_method_scrub_report_t r;
+    uint64_t t;
+    uint32_t w;
+    int rc;
+
+    rc = report_args(loc, report, cap, idx, val);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    if (!scrub_on_host(NULL, 0, NULL, 0, NULL, 0, loc, report) ||
+        !scrub_on_host(NULL, 0, NULL, 0, NULL, 0, idx, val))
+        return -EINVAL;
+    memset(&r, 0, sizeof(r));
+    for (t = 0; t < nstripes; t++) {
+        w = loc[t];
+        if (w == 0)
+            continue;
+        if (r.nbad < cap) {
+            idx[r.nbad] = t;
+            if (val)
+                val[r.nbad] = w;
+        }
+        r.nbad++;
+        r.nmany += w >> 31;
+        for (w &= ~EC_MI355X_LOCATE_MANY; w; w &= w - 1)
+            r.brick[__builtin_ctz(w)]++;
+    }
+    r.listed = r.nbad < cap ? r.nbad : cap;
+    *report = r;
+    return 0;
+}
+
+/* The order of the family, except that the weak symbol comes before the look
+ * at where the buffers live: a build without the device layer calls every
+ * pointer host memory, and would answer -EINVAL to any call otherwise. */
+static int32_t
+ecm_scrub_report_device_impl(int device, void *stream, uint64_t nstripes, const uint32_t *loc,
+                             ec_method_scrub_report_t *report, uint64_t cap, uint64_t *idx,
+                             uint32_t *val, void *work, size_t work_bytes)
+{
+    int rc;
+
+    rc = report_args(loc, report, cap, idx, val);
+    if (rc)
+        return rc;
+    if ((uintptr_t)work & 7u)
+        return -EINVAL;
+    if (nstripes == 0)
+        return 0;
+    if (!work || work_bytes < ECD_REPORT_WORK(nstripes) ||
+        nstripes > ECD_REPORT_MAX_STRIPES)
+        return -EINVAL;
+    if (!ecd_scrub_report)
+        return -ENODEV;
+    if (!scrub_on_device(device, NULL, 0, NULL, 0, NULL, 0, loc, report) ||
+        !scrub_on_device(device, NULL, 0, NULL, 0, NULL, 0, idx, val) ||
+        !scrub_on_device(device, NULL, 0, NULL, 0, NULL, 0, work, NULL))
+        return -EINVAL;
+    return ecd_scrub_report(device, stream, nstripes, loc, (uint64_t *)report, cap, idx, val,
+                            work);
+}
+
 /* ------------------------------------------------- partial-stripe writes */
 
 static int32_t
@@ -4452,6 +4544,32 @@ ec_method_repair2_device(ec_matrix_list_t *list, int device, void *stream, uint6
     const uint64_t seq = ecd_error_seq();
     return ecm_ret("ec_method_repair2_device", seq,
                    repair_device(list, device, stream, nstripes, avail_mask, frags, loc, 1));
+}
+
+size_t
+ec_method_scrub_report_work(uint64_t nstripes)
+{
+    return (size_t)ECD_REPORT_WORK(nstripes);
+}
+
+int32_t
+ec_method_scrub_report(uint64_t nstripes, const uint32_t *loc, ec_method_scrub_report_t *report,
+                       uint64_t cap, uint64_t *idx, uint32_t *val)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_scrub_report", seq,
+                   ecm_scrub_report_impl(nstripes, loc, report, cap, idx, val));
+}
+
+int32_t
+ec_method_scrub_report_device(int device, void *stream, uint64_t nstripes, const uint32_t *loc,
+                              ec_method_scrub_report_t *report, uint64_t cap, uint64_t *idx,
+                              uint32_t *val, void *work, size_t work_bytes)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_scrub_report_device", seq,
+                   ecm_scrub_report_device_impl(device, stream, nstripes, loc, report, cap, idx,
+                                                val, work, work_bytes));
 }
 
 int32_t

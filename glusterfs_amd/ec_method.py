@@ -63,6 +63,7 @@ EXPORTS = (
     "ec_method_heal_checked2", "ec_method_heal_checked2_device",
     "ec_method_decode_verified", "ec_method_decode_verified_device",
     "ec_method_heal_verified", "ec_method_heal_verified_device",
+    "ec_method_scrub_report", "ec_method_scrub_report_device", "ec_method_scrub_report_work",
 )
 
 
@@ -118,6 +119,15 @@ class PoolStats(ctypes.Structure):
         "pool_bytes", "in_use_bytes", "gets", "misses", "slabs", "slab_register_us",
         "deferred_registers", "deferred_register_us", "deferred_register_failures",
         "unregisters", "unregister_us")]
+
+
+class ScrubReport(ctypes.Structure):
+    """ec_method_scrub_report_t: the counts of a loc[] / bad[] array."""
+    _fields_ = [("nbad", ctypes.c_uint64), ("nmany", ctypes.c_uint64),
+                ("listed", ctypes.c_uint64), ("brick", ctypes.c_uint64 * EC_MAX_NODES)]
+
+
+assert ctypes.sizeof(ScrubReport) == 272
 
 
 class Config(ctypes.Structure):
@@ -194,6 +204,10 @@ def _load():
         "ec_method_repair2": (i32, [P, u64, up, vp, vp, ctypes.POINTER(u64),
                                     ctypes.POINTER(u64)]),
         "ec_method_repair2_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
+        "ec_method_scrub_report_work": (ctypes.c_size_t, [u64]),
+        "ec_method_scrub_report": (i32, [u64, vp, vp, u64, vp, vp]),
+        "ec_method_scrub_report_device": (i32, [ctypes.c_int, vp, u64, vp, vp, u64, vp, vp, vp,
+                                                ctypes.c_size_t]),
         "ec_method_encode_device": (i32, [P, ctypes.c_int, vp, u64, vp, vp]),
         "ec_method_decode_device": (i32, [P, ctypes.c_int, vp, u64, up, vp, vp]),
         "ec_method_decode_mixed_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, u32, vp,
@@ -811,6 +825,43 @@ class ECMatrixList:
 
 def sync_device(device, stream=None):
     return _check(lib.ec_method_sync_device(device, stream), "ec_method_sync_device")
+
+
+# --- the report of a scrub --------------------------------------------------
+def scrub_report_work(nstripes):
+    """ec_method_scrub_report_work: bytes of scratch scrub_report_device wants
+    for `nstripes` (no device needed)."""
+    return lib.ec_method_scrub_report_work(nstripes)
+
+
+def scrub_report(loc, cap=0):
+    """ec_method_scrub_report: count and list the dirty stripes of `loc`, a
+    numpy uint32 array any call of the scrub family wrote (loc[] or bad[]).
+    Returns (ScrubReport, idx, val): the indices (uint64) and values (uint32)
+    of the first min(nbad, cap) non-zero entries, in ascending order."""
+    import numpy as np
+    loc = np.ascontiguousarray(loc, dtype=np.uint32)
+    rep = ScrubReport()
+    idx, val = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+    _check(lib.ec_method_scrub_report(loc.size, loc.ctypes.data, ctypes.addressof(rep), cap,
+                                      idx.ctypes.data if cap else None,
+                                      val.ctypes.data if cap else None),
+           "ec_method_scrub_report")
+    return rep, idx[:rep.listed], val[:rep.listed]
+
+
+def scrub_report_device(device, stream, nstripes, loc, report, cap, idx, val, work,
+                        work_bytes=None):
+    """ec_method_scrub_report_device: the same on device buffers (`report`,
+    272 bytes, `idx`, `val` and the scratch `work` too), queued on `stream`
+    behind whatever writes `loc`.  `val` may be None, `idx` too when cap is 0;
+    `work` holds at least scrub_report_work(nstripes) bytes (work_bytes: its
+    size, by default that of the buffer object)."""
+    if work_bytes is None:
+        work_bytes = 0 if work is None else _nbytes(work)
+    return _check(lib.ec_method_scrub_report_device(
+        device, stream, nstripes, addr(loc), addr(report), cap, addr(idx), addr(val), addr(work),
+        work_bytes), "ec_method_scrub_report_device")
 
 
 # --- on-disk format guard (trusted.ec.config) ------------------------------

@@ -675,6 +675,68 @@ int32_t ec_method_repair2_device(ec_matrix_list_t *list, int device, void *strea
                                  uint64_t nstripes, uintptr_t avail_mask,
                                  void *const *frags, const uint32_t *loc);
 
+/* The report of a scrub: the last stage behind any call above that writes
+ * loc[] or bad[].  Their device variants count nothing, which left a caller
+ * to copy 4 bytes per stripe to the host, or to write a kernel, to learn what
+ * it acts on: how many stripes are dirty, how many of them are
+ * EC_MI355X_LOCATE_MANY (its -EIO), and which ones they are.  This call gives
+ * exactly that, where loc[] lies.  It takes no list: loc[0..nstripes) is any
+ * array of the family, from any volume (bad[] simply never has bit 31), and
+ * is read and never written.
+ *
+ *   report->nbad      stripes with loc[t] != 0
+ *   report->nmany     of those, stripes with bit 31 (EC_MI355X_LOCATE_MANY) set
+ *   report->brick[i]  stripes with bit i of loc[t] set, i < 31
+ *   report->listed    min(nbad, cap): the entries written to idx[] and val[]
+ *   idx[r]            the index t of the r-th dirty stripe, ascending, r < listed
+ *   val[r]            loc[idx[r]], r < listed
+ * The counts are over all nstripes whatever cap is, so listed < nbad says that
+ * the list was cut.  Nothing at or past listed is written.  val may be NULL
+ * (indices only); idx may be NULL only when cap == 0 (counts only).  A word
+ * with bit 31 and other bits counts once in nbad, once in nmany and in the
+ * brick[i] of every bit it has, and is listed as it is.  The result is a
+ * function of loc[] and cap alone, byte for byte: from run to run, and
+ * between the host and the device variant.
+ *
+ * The device variant takes every buffer on `device` -- loc, report, idx, val
+ * and work -- and is asynchronous on `stream`: it can be queued right behind
+ * the call that writes loc[] with no host synchronisation, and the host then
+ * copies 272 + 12 * listed bytes instead of 4 * nstripes.  It pre-zeroes
+ * nothing, uploads nothing, allocates nothing and uses no global atomics, and
+ * no block of it waits on another; every output word is written by one plain
+ * store.  work is scratch of at least ec_method_scrub_report_work(nstripes)
+ * bytes, 8-byte aligned; its content is undefined before and after the call,
+ * and calls that may overlap in time need distinct work.
+ * ec_method_scrub_report_work needs no device, is non-decreasing in nstripes
+ * and is 0 only for nstripes == 0 (140 bytes per 4096 stripes, DESIGN.md
+ * 3.24).
+ *
+ * -EINVAL: a NULL loc or report; loc or val not 4-byte aligned; report, idx
+ * or work not 8-byte aligned; cap > 0 with a NULL idx; nstripes > 0 with a
+ * NULL work or work_bytes too small; nstripes above 2^40 (device variant);
+ * host and device buffers mixed, or given to the wrong entry point.
+ * nstripes == 0 returns 0 after these checks and writes nothing, the report
+ * included.  -ENODEV where the device layer lacks the call.
+ *
+ * The host variant is one loop on the calling thread; like the other scrub
+ * host calls it leaves ec_method_stats_t, the router and the run-time
+ * compiler alone. */
+typedef struct {
+    uint64_t nbad;    /* stripes with loc[t] != 0 */
+    uint64_t nmany;   /* of those, stripes with EC_MI355X_LOCATE_MANY (bit 31) set */
+    uint64_t listed;  /* entries written to idx[] / val[]: min(nbad, cap) */
+    uint64_t brick[EC_MI355X_MAX_NODES]; /* brick[i] = stripes with bit i of loc[t] set */
+} ec_method_scrub_report_t;              /* 272 bytes, no padding */
+
+size_t ec_method_scrub_report_work(uint64_t nstripes);
+int32_t ec_method_scrub_report(uint64_t nstripes, const uint32_t *loc,
+                               ec_method_scrub_report_t *report, uint64_t cap, uint64_t *idx,
+                               uint32_t *val);
+int32_t ec_method_scrub_report_device(int device, void *stream, uint64_t nstripes,
+                                      const uint32_t *loc, ec_method_scrub_report_t *report,
+                                      uint64_t cap, uint64_t *idx, uint32_t *val, void *work,
+                                      size_t work_bytes);
+
 /* Partial-stripe write: the read-modify-write of
  * ec_writev_start (ec-inode-write.c:1987-2085) fused with ec_writev_encode.
  * The write's user data is the iovec list iov[0..count) (as the writev fop
