@@ -234,6 +234,19 @@ int ecd_writev_encode_device(int device, void *stream, uint32_t k, uint32_t n, u
                              uint64_t user_size, const void *user, const void *old_head,
                              const void *old_tail, void *const *out, const uint8_t *enc_pat);
 
+/* Read of an unaligned byte range on device memory (asynchronous on
+ * `stream`; ec_method_readv_decode_device): with S = 512 k and ns = ceil((head
+ * + size) / S), in[0..k) are fragments of ns * 512 bytes, inv[j * k + p] their
+ * decode matrix, and dst[0 .. size) gets bytes [head, head + size) of the ns *
+ * S bytes they decode to (head < S, size > 0).  The stripes wholly inside the
+ * range run ecd_combine's launch with the output at dst + t * S - head; the
+ * first and the last stripe, where the range covers them in part, run one
+ * launch of ec_decode_clip, which stores the covered bytes alone.  Nothing
+ * outside dst[0 .. size) is written, nothing is allocated or uploaded; in and
+ * dst may have any byte alignment. */
+int ecd_readv_decode_device(int device, void *stream, uint32_t k, uint64_t head, uint64_t size,
+                            const void *const *in, const uint8_t *inv, void *dst);
+
 /* Decode / reconstruct: frags[0..nfrags) are fragment buffers of
  * nstripes*512 bytes (NULL for fragments no pattern reads).  Output: when
  * outs is NULL, out = nstripes*rows*512 bytes, stripe-major (decoded data);

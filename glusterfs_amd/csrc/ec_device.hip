@@ -1858,6 +1858,51 @@ int ecd_writev_encode_device(int device, void *stream, uint32_t k, uint32_t n, u
     return rc;
 }
 
+int ecd_readv_decode_device(int device, void *stream, uint32_t k, uint64_t head, uint64_t size,
+                            const void *const *in, const uint8_t *inv, void *dst)
+{
+    const uint64_t S = (uint64_t)k * ECD_CHUNK;
+    if (k == 0 || k > ECD_MAX_K || head >= S || size == 0 || !in || !inv || !dst)
+        return -EINVAL;
+    /* byte o of stripe t belongs at d0 + t * S + o; d0 may lie in front of dst */
+    const uintptr_t d0 = (uintptr_t)dst - (uintptr_t)head;
+    const uint64_t end = head + size;
+    const uint64_t first_whole = head ? 1 : 0, whole_end = end / S;
+    ecdk_clip_edge_t edge[2];
+    uint32_t nedges = 0;
+    if (head != 0 || end < S) /* the first stripe, cut at one end or both */
+        edge[nedges++] = {0, reinterpret_cast<uint8_t *>(d0), (uint32_t)head,
+                          (uint32_t)(end < S ? end : S)};
+    if (whole_end >= 1 && end % S != 0) /* another stripe, in which the range ends */
+        edge[nedges++] = {whole_end, reinterpret_cast<uint8_t *>(d0 + whole_end * S), 0,
+                          (uint32_t)(end % S)};
+    return on_device(device, stream, [&](hipStream_t s) {
+        int rc = 0;
+        if (whole_end > first_whole) {
+            /* the stripes wholly inside the range: ec_method_decode_device's
+             * combine, its output wherever the range puts it */
+            ecd_combine_desc_t d;
+            memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+            d.k = d.rows = k;
+            d.nstripes = whole_end - first_whole;
+            d.npatterns = 1;
+            d.pat_bytes = k + k * k;
+            d.in_stride = ECD_CHUNK;
+            d.out_stride = S;
+            for (uint32_t p = 0; p < k; ++p) {
+                d.in_base[p] = static_cast<const uint8_t *>(in[p]) + first_whole * ECD_CHUNK;
+                d.out_base[p] = reinterpret_cast<uint8_t *>(d0 + first_whole * S + p * ECD_CHUNK);
+                d.pat[p] = (uint8_t)p;
+            }
+            memcpy(d.pat + k, inv, (size_t)k * k);
+            rc = ecdk_combine(s, &d);
+        }
+        if (rc == 0 && nedges)
+            rc = ecdk_decode_clip(s, k, in, inv, nedges, edge);
+        return rc;
+    });
+}
+
 int ecd_decode_host(int ndev, uint32_t k, uint32_t rows, uint64_t nstripes, uint32_t nfrags,
                     const void *const *frags, void *out, void *const *outs, uint32_t npatterns,
                     const uint8_t *pats, const uint8_t *group_pattern, uint32_t group_shift)

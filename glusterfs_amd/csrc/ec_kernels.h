@@ -43,6 +43,17 @@ int ecdk_decode_verified(hipStream_t s, const ecd_combine_desc_t *d, const void 
 int ecdk_heal_verified(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                        const uint8_t *check_brick, uint32_t ntargets, const uint8_t *heal,
                        void *const *out, uint32_t *bad);
+/* The partly covered stripes of ecd_readv_decode_device (ec_decode_clip):
+ * stripe t of the k fragments is decoded and bytes [lo, hi) of its k * 512 go
+ * to base + lo .. base + hi, nothing else is written.  base is where byte 0 of
+ * the stripe would lie and may point in front of the caller's buffer. */
+typedef struct ecdk_clip_edge {
+    uint64_t t;
+    uint8_t *base;
+    uint32_t lo, hi;
+} ecdk_clip_edge_t;
+int ecdk_decode_clip(hipStream_t s, uint32_t k, const void *const *in, const uint8_t *inv,
+                     uint32_t nedges, const ecdk_clip_edge_t *edge);
 /* the one or two damaged bricks per stripe of ecd_locate2 (ec_locate2_n) */
 int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                  const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,

@@ -1249,6 +1249,48 @@ int ecdk_heal_verified(hipStream_t s, const ecd_combine_desc_t *d, const void *c
     });
 }
 
+/* ------------------------------------------- ranged read: the edge stripes */
+
+/* in: the k fragments (device memory, any byte alignment); inv: k x k bytes,
+ * the decode matrix of those fragments; edge[0 .. nedges): the one or two
+ * stripes to decode and the bytes of each to store.  One launch of one block
+ * per edge; inv and the clips travel in the kernel arguments. */
+int ecdk_decode_clip(hipStream_t s, uint32_t k, const void *const *in, const uint8_t *inv,
+                     uint32_t nedges, const ecdk_clip_edge_t *edge)
+{
+    static_assert(sizeof(DecodeClipArgs) <= 2048, "inv must fit the kernel arguments");
+    DecodeClipArgs a;
+    if (k == 0 || k > ECD_MAX_K || !in || !inv || !edge || nedges == 0 || nedges > 2)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    a.k = k;
+    a.kw = (k + 3) / 4;
+    for (u32 p = 0; p < k; ++p) {
+        if (!in[p])
+            return -EINVAL;
+        a.in[p] = static_cast<const uint8_t *>(in[p]);
+    }
+    for (u32 e = 0; e < nedges; ++e) {
+        if (edge[e].lo >= edge[e].hi || edge[e].hi > k * ECD_CHUNK)
+            return -EINVAL;
+        a.t[e] = edge[e].t;
+        a.base[e] = edge[e].base;
+        a.lo[e] = edge[e].lo;
+        a.hi[e] = edge[e].hi;
+    }
+    pack_rows(a.inv, 0, k, k, a.kw, inv);
+    /* one stripe in slot 0 of a scrub tile: at most 32 KiB */
+    const size_t lds = scrub_tile_lds(k, 0);
+    /* the k -> K buckets and wave counts of launch_scrub_tile */
+    if (k <= 4)
+        hipLaunchKernelGGL((ec_decode_clip<4, 4>), dim3(nedges), dim3(4 * 64), lds, s, a);
+    else if (k <= 8)
+        hipLaunchKernelGGL((ec_decode_clip<8, 8>), dim3(nedges), dim3(8 * 64), lds, s, a);
+    else
+        hipLaunchKernelGGL((ec_decode_clip<16, 8>), dim3(nedges), dim3(8 * 64), lds, s, a);
+    return launch_ok("launch_decode_clip");
+}
+
 /* ------------------------------------------ locating up to two bricks */
 
 /* The arguments of ec_locate2_n from what ecdk_locate2 is given: pack_locate,

@@ -2358,6 +2358,80 @@ __global__ __launch_bounds__(NW * 64) void ec_heal_verified_n(const HealVerified
         a.bad[t.t0 + t.tid] = t.flags[t.tid];
 }
 
+/* ------------------------------------------- ranged read: the edge stripes */
+
+/* Kernel arguments of ec_decode_clip: the k fragments, inv(mask) (k rows of kw
+ * words, a byte per input) and, for each of the one or two blocks, the stripe
+ * it decodes (chunk t[e] of every fragment), the address base[e] that byte 0
+ * of that stripe's data would have in the caller's buffer -- it may lie in
+ * front of the buffer: only bytes [lo[e], hi[e]) of the stripe are stored, at
+ * base[e] + lo[e] .. base[e] + hi[e].  440 bytes. */
+struct DecodeClipArgs {
+    const uint8_t *in[ECD_MAX_K];
+    uint8_t *base[2];
+    uint64_t t[2];
+    u32 lo[2], hi[2];
+    u32 k, kw;
+    u32 inv[ECD_MAX_K * ECD_MAX_K / 4];
+};
+
+/* store_chunk for a chunk that the clip [lo, hi) of its stripe may cut: the
+ * lane's dword of plane b sits at stripe offset off + 64 b.  A dword wholly
+ * inside the clip leaves by one dword store, one that straddles lo or hi by a
+ * byte store for each byte inside, and one outside is not stored. */
+__device__ __forceinline__ void store_chunk_clipped(uint8_t *base, u32 off, u32 lo, u32 hi,
+                                                    const u32 (&d)[8][1])
+{
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const u32 o = off + (u32)b * 64u;
+        const u32 w = d[b][0];
+        if (o >= lo && o + 4u <= hi) {
+            *reinterpret_cast<u32 *>(base + o) = w;
+        } else {
+#pragma unroll
+            for (u32 i = 0; i < 4; ++i)
+                if (o + i >= lo && o + i < hi)
+                    base[o + i] = (uint8_t)(w >> (8u * i));
+        }
+    }
+}
+
+/* ec_method_readv_decode_device: the one or two stripes that an unaligned
+ * range covers in part.  Block e decodes stripe t[e] and stores bytes [lo[e],
+ * hi[e]) of it, no byte more.  The k chunks are staged into slot 0 of a scrub
+ * tile (one stripe: lanes 0 .. 15 of a wave hold its 16 dword columns, the
+ * other lanes run along and store nothing), the k output rows are spread over
+ * the waves as in scrub_decode, and a row that the clip leaves out entirely
+ * (wave-uniform) is not computed. */
+template <int K, int NW>
+__global__ __launch_bounds__(NW * 64) void ec_decode_clip(const DecodeClipArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const bool e = blockIdx.x != 0;
+    const u32 tid = threadIdx.x;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    const u32 k = a.k;
+    const uint64_t t = e ? a.t[1] : a.t[0];
+    const u32 lo = e ? a.lo[1] : a.lo[0], hi = e ? a.hi[1] : a.hi[0];
+    uint8_t *base = e ? a.base[1] : a.base[0];
+    stage_tile<kScrubT, NW>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        return a.in[p] + st * ECD_CHUNK;
+    }, k, t, t + 1, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    const uint8_t *col = lds + cs * 64u + cc * 4u;
+    for (u32 j = wave; j < k; j += NW) {
+        if ((j + 1) * ECD_CHUNK <= lo || j * ECD_CHUNK >= hi)
+            continue;
+        u32 acc[8][1];
+        row_product<K>(a.inv, j, a.kw, k, col, acc);
+        if (cs == 0)
+            store_chunk_clipped(base, j * ECD_CHUNK + cc * 4u, lo, hi, acc);
+    }
+}
+
 /* ------------------------------------------- repairing the named chunks */
 
 /* Kernel arguments of ec_repair_n.  frag[] is indexed by brick (null outside

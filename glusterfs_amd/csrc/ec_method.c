@@ -4087,6 +4087,164 @@ ecm_writev_encode_device_impl(ec_matrix_list_t *list, int device, void *stream, 
                                     old_tail, out, ctx->enc_pat);
 }
 
+/* ------------------------------------------------ unaligned byte-range reads */
+
+/* Weak like ecd_decode_verified: without the symbol
+ * ec_method_readv_decode_device is -ENODEV. */
+extern __typeof__(ecd_readv_decode_device) ecd_readv_decode_device __attribute__((weak));
+
+/* an argument error of the ranged read, with its reason for
+ * ec_method_last_error() */
+static int
+readv_inval(const char *why)
+{
+    char buf[160];
+
+    snprintf(buf, sizeof buf, "ec_method_readv_decode: %s", why);
+    ecd_set_error(buf);
+    return -EINVAL;
+}
+
+/* What both entry points check first: the list, the k fragments and a range
+ * that starts inside its first stripe.  pat gets the pattern of
+ * ec_method_decode_device: input p is the p-th brick of the mask, the
+ * coefficients are inv(mask) from the list's cache. */
+static int
+readv_args(ec_matrix_list_t *list, uint64_t head, uintptr_t mask, const void *const *in,
+           uint8_t *pat)
+{
+    uint32_t rows[ECM_MAX_K], k, p;
+    uint8_t src[ECM_MAX_K];
+    ecm_matrix_t *m;
+
+    if (!list || !CTX(list))
+        return readv_inval("no list");
+    if (!in)
+        return readv_inval("no fragment list");
+    k = list->columns;
+    if (head >= (uint64_t)k * EC_METHOD_CHUNK_SIZE)
+        return readv_inval("head is not inside the first stripe");
+    /* rows_from_mask writes a row for every bit: count them first */
+    if (popcount_mask(mask) != k)
+        return readv_inval("the mask is not k bricks of the volume");
+    rows_from_mask(mask, rows);
+    if (!mask_rows_ok(list, mask, rows))
+        return readv_inval("the mask is not k bricks of the volume");
+    for (p = 0; p < k; p++) {
+        if (!in[p])
+            return readv_inval("a fragment is NULL");
+        src[p] = (uint8_t)p;
+    }
+    m = matrix_get(list, mask, rows);
+    if (!m)
+        return -ENOMEM;
+    pack_pattern(pat, k, src, k, m->inv);
+    matrix_put(list, m);
+    return 0;
+}
+
+/* The byte-exact specification of the ranged read, on the calling thread's
+ * CPU engine.  pos walks D from head to the end of the range and (c, so) is
+ * the place in the segments that receives D[pos].  A run of whole stripes
+ * that one segment takes is decoded into it; any other stripe -- an edge, or
+ * one that a segment boundary cuts -- is decoded into buf and its live bytes
+ * are copied out. */
+static int32_t
+ecm_readv_decode_impl(ec_matrix_list_t *list, uint64_t head, uintptr_t mask,
+                      const void *const *in, const struct iovec *iov, int count)
+{
+    uint8_t buf[ECM_MAX_K * EC_METHOD_CHUNK_SIZE];
+    ecd_combine_desc_t d;
+    uint64_t size = 0, S, end, pos, t, n, room, so = 0, lo, hi;
+    uint32_t k, p;
+    int c, rc;
+
+    if (count < 0)
+        return readv_inval("count is negative");
+    if (count > 0 && !iov)
+        return readv_inval("no segment list");
+    rc = readv_args(list, head, mask, in, d.pat);
+    if (rc)
+        return rc;
+    for (c = 0; c < count; c++) {
+        if (iov[c].iov_len && !iov[c].iov_base)
+            return readv_inval("a segment is NULL");
+        size += iov[c].iov_len;
+    }
+    if (size == 0)
+        return 0;
+    k = list->columns;
+    for (c = 0; c < count; c++)
+        if (iov[c].iov_len && ecd_ptr_device(iov[c].iov_base) >= 0)
+            return readv_inval("a segment is device memory");
+    if (!bufs_on(in, k, -1))
+        return readv_inval("a fragment is device memory");
+    S = (uint64_t)k * EC_METHOD_CHUNK_SIZE;
+    end = head + size;
+    desc_init(&d, k, k, 0, EC_METHOD_CHUNK_SIZE, S);
+    for (c = 0, pos = head; pos < end;) {
+        while (so == iov[c].iov_len) { /* size bytes are left in the segments */
+            c++;
+            so = 0;
+        }
+        t = pos / S;
+        room = iov[c].iov_len - so;
+        n = pos % S == 0 ? (room < end - pos ? room : end - pos) / S : 0;
+        for (p = 0; p < k; p++) {
+            d.in_base[p] = (const uint8_t *)in[p] + t * EC_METHOD_CHUNK_SIZE;
+            d.out_base[p] = (n ? (uint8_t *)iov[c].iov_base + so : buf) +
+                            (size_t)p * EC_METHOD_CHUNK_SIZE;
+        }
+        d.nstripes = n ? n : 1;
+        rc = ecc_combine(CTX(list)->isa, &d);
+        if (rc)
+            return rc;
+        if (n) {
+            pos += n * S;
+            so += n * S;
+            continue;
+        }
+        lo = pos - t * S;
+        hi = end - t * S < S ? end - t * S : S;
+        while (lo < hi) {
+            while (so == iov[c].iov_len) {
+                c++;
+                so = 0;
+            }
+            room = iov[c].iov_len - so;
+            n = room < hi - lo ? room : hi - lo;
+            memcpy((uint8_t *)iov[c].iov_base + so, buf + lo, n);
+            lo += n;
+            so += n;
+        }
+        pos = t * S + hi;
+    }
+    return 0;
+}
+
+static int32_t
+ecm_readv_decode_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t head,
+                             uint64_t size, uintptr_t mask, const void *const *in, void *dst)
+{
+    uint8_t pat[ECM_MAX_K + ECM_MAX_K * ECM_MAX_K];
+    uint32_t k;
+    int rc;
+
+    if (!dst)
+        return readv_inval("no destination");
+    rc = readv_args(list, head, mask, in, pat);
+    if (rc)
+        return rc;
+    if (size == 0)
+        return 0;
+    if (!ecd_readv_decode_device)
+        return -ENODEV;
+    k = list->columns;
+    if (!scrub_on_device(device, in, k, NULL, 0, NULL, 0, dst, NULL))
+        return readv_inval("a buffer is not memory of the device");
+    return ecd_readv_decode_device(device, stream, k, head, size, in, pat + k, dst);
+}
+
 /* ---------------------------------------------------- device-resident */
 
 static int32_t
@@ -4590,6 +4748,25 @@ ec_method_writev_encode_device(ec_matrix_list_t *list, int device, void *stream,
     return ecm_ret("ec_method_writev_encode_device", seq,
                    ecm_writev_encode_device_impl(list, device, stream, head, size, user, old_head,
                                                  old_tail, out));
+}
+
+int32_t
+ec_method_readv_decode(ec_matrix_list_t *list, uint64_t head, uintptr_t mask,
+                       const void *const *in, const struct iovec *iov, int count)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_readv_decode", seq,
+                   ecm_readv_decode_impl(list, head, mask, in, iov, count));
+}
+
+int32_t
+ec_method_readv_decode_device(ec_matrix_list_t *list, int device, void *stream, uint64_t head,
+                              uint64_t size, uintptr_t mask, const void *const *in, void *dst)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_readv_decode_device", seq,
+                   ecm_readv_decode_device_impl(list, device, stream, head, size, mask, in,
+                                                dst));
 }
 
 int32_t

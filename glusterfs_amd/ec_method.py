@@ -64,6 +64,7 @@ EXPORTS = (
     "ec_method_decode_verified", "ec_method_decode_verified_device",
     "ec_method_heal_verified", "ec_method_heal_verified_device",
     "ec_method_scrub_report", "ec_method_scrub_report_device", "ec_method_scrub_report_work",
+    "ec_method_readv_decode", "ec_method_readv_decode_device",
 )
 
 
@@ -245,6 +246,8 @@ def _load():
         "ec_method_writev_encode": (i32, [P, u64, vp, ctypes.c_int, vp, vp, vp]),
         "ec_method_writev_encode_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, vp, vp,
                                                  vp]),
+        "ec_method_readv_decode": (i32, [P, u64, up, vp, vp, ctypes.c_int]),
+        "ec_method_readv_decode_device": (i32, [P, ctypes.c_int, vp, u64, u64, up, vp, vp]),
         "ec_method_config_fill": (None, [u32, u32, ctypes.POINTER(Config)]),
         "ec_method_config_pack": (i32, [ctypes.POINTER(Config), vp]),
         "ec_method_config_unpack": (i32, [vp, ctypes.c_size_t, ctypes.POINTER(Config)]),
@@ -568,6 +571,22 @@ class ECMatrixList:
         return _check(lib.ec_method_writev_encode_device(
             ctypes.byref(self._list), device, stream, head, size, addr(user), addr(old_head),
             addr(old_tail), _ptr_array(out)), "ec_method_writev_encode_device")
+
+    def readv_decode(self, head, mask, inp, out):
+        """ec_method_readv_decode: `out` is one buffer or a list of buffers
+        (the readv iovec list) that together take the bytes of the range, which
+        starts `head` bytes into the first stripe of the k fragments `inp`."""
+        bufs = out if isinstance(out, (list, tuple)) else [out]
+        iov = (_IOVec * len(bufs))(*[_IOVec(addr(b), _nbytes(b)) for b in bufs])
+        return _check(lib.ec_method_readv_decode(ctypes.byref(self._list), head, mask,
+                                                 _ptr_array(inp), iov, len(bufs)),
+                      "ec_method_readv_decode")
+
+    def readv_decode_device(self, device, stream, head, size, mask, inp, out):
+        """ec_method_readv_decode_device: `out` takes exactly `size` bytes."""
+        return _check(lib.ec_method_readv_decode_device(
+            ctypes.byref(self._list), device, stream, head, size, mask, _ptr_array(inp),
+            addr(out)), "ec_method_readv_decode_device")
 
     def heal(self, nstripes, mask, inp, target_mask, out):
         return _check(lib.ec_method_heal(ctypes.byref(self._list), nstripes, mask,

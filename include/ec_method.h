@@ -759,6 +759,61 @@ int32_t ec_method_writev_encode(ec_matrix_list_t *list, uint64_t head, const str
                                 int count, const void *old_head, const void *old_tail,
                                 void *const *out);
 
+/* Read of an unaligned byte range: the read counterpart of the call above.
+ * ec_readv rounds the offset of a read down to its stripe and keeps fop->head
+ * = offset % stripe (ec-inode-read.c:1360-1362); after the decode it trims the
+ * answer to the user's range by pointer arithmetic into its own buffer
+ * (:1202-1217).  A caller whose destination is a buffer of exactly `size`
+ * bytes, in device memory above all, has no such trick, and the whole-stripe
+ * decode would write `head` bytes in front of it and the padding behind it.
+ * These calls decode the stripes the range touches and write the bytes of the
+ * range, no byte more.
+ *
+ * S = 512 * k is the stripe.  head < S is the offset of the first user byte
+ * inside its stripe (fop->head); size is the sum of the iov_len (host
+ * variant) or the argument (device variant), and ns = ceil((head + size) / S)
+ * stripes are touched.  mask and in are as for the device-resident decode
+ * below: mask has exactly k bits below n, in[p] is the fragment of the p-th
+ * set bit, ns * 512 bytes long, and starts at the chunk of the stripe that
+ * holds the first user byte.  With D the ns * S bytes that the whole-stripe
+ * decode gives for those fragments and that mask, the call writes D[head ..
+ * head + size): to dst[0 .. size) (device variant), or to the segments
+ * iov[0 .. count) in order (host variant; segments of length 0 are allowed).
+ *
+ * No byte outside [dst, dst + size), or outside the segments, is written;
+ * nothing of in[p] is read at or past ns * 512, and nothing in `in` is
+ * written.  dst, every iov_base and the fragments may have any byte
+ * alignment.  head == 0 with size % S == 0 is byte for byte the
+ * device-resident decode and runs the same launch; every other range gives
+ * the bytes that a decode into a temporary followed by a copy would give.
+ * size == 0 returns 0 after the argument checks and writes nothing.
+ *
+ * -EINVAL: a NULL list, in, dst, or iov with count > 0; count < 0; a NULL
+ * in[p]; a NULL iov_base with a non-zero length; head >= S; a mask that is
+ * not exactly k bricks below n; host and device buffers mixed, or given to the
+ * wrong entry point.  -ENODEV where the device layer lacks the call.
+ *
+ * The device variant is asynchronous on `stream` with no host
+ * synchronisation.  It allocates nothing and uploads nothing -- inv(mask) and
+ * the clip travel in the kernel arguments -- pre-zeroes nothing, uses no
+ * global atomics and issues at most two launches: the whole-stripe combine
+ * for the stripes that lie inside the range, unchanged, with its output at
+ * dst + t * S - head, and one small kernel for the first and the last stripe
+ * where the range covers them in part, which stores the covered bytes alone.
+ *
+ * The host variant runs on the calling thread's CPU engine whatever the
+ * volume's engine is; like the scrub family's host calls it leaves
+ * ec_method_stats_t, the router and the run-time compiler alone.  Interior
+ * stripes that lie whole inside one segment are decoded straight into it; an
+ * edge stripe, or one that a segment boundary cuts, is decoded into an S-byte
+ * buffer on the stack and its live bytes are copied out.  It does not go to
+ * the GPU because the host read of the xlator trims for free
+ * (ec-inode-read.c:1202): this variant is the byte-exact specification, the
+ * path of a CPU-only node and what runs without a GPU.  Large host reads keep
+ * using the whole-stripe decode. */
+int32_t ec_method_readv_decode(ec_matrix_list_t *list, uint64_t head, uintptr_t mask,
+                               const void *const *in, const struct iovec *iov, int count);
+
 /* Device-resident, asynchronous variants for callers that keep stripes in
  * MI355X memory: all buffers are device pointers on `device` (index among
  * the visible gfx950 devices), work is queued on `stream` (a hipStream_t;
@@ -793,6 +848,10 @@ int32_t ec_method_writev_encode_device(ec_matrix_list_t *list, int device, void 
                                        uint64_t head, uint64_t size, const void *user,
                                        const void *old_head, const void *old_tail,
                                        void *const *out);
+/* the unaligned read above on device buffers: dst gets exactly size bytes */
+int32_t ec_method_readv_decode_device(ec_matrix_list_t *list, int device, void *stream,
+                                      uint64_t head, uint64_t size, uintptr_t mask,
+                                      const void *const *in, void *dst);
 int32_t ec_method_sync_device(int device, void *stream);
 
 /* ------------------------------------------------------------------------
