@@ -247,6 +247,25 @@ int ecd_writev_encode_device(int device, void *stream, uint32_t k, uint32_t n, u
 int ecd_readv_decode_device(int device, void *stream, uint32_t k, uint64_t head, uint64_t size,
                             const void *const *in, const uint8_t *inv, void *dst);
 
+/* Write of an unaligned byte range over stored fragments, on device memory
+ * (asynchronous on `stream`; ec_method_writev_rmw_device): with S = 512 k, end
+ * = head + size and ns = ceil(end / S), user[0 .. size) replaces bytes [head,
+ * end) of ns stripes and out[0..n) get the ns chunks of their encode.
+ * old_head[0..k) / old_tail[0..k) are the stored chunks of the first / last
+ * stripe on the k bricks that inv (k x k bytes, inv[j * k + p]) decodes, or
+ * NULL for a stripe of zeros; with ns == 1 the stripe's old content is
+ * old_head, or old_tail when old_head is NULL.  enc_pat: src[k] then the n x k
+ * encode matrix.  The stripes that the write covers wholly run the launch of
+ * ec_method_encode_device on user + t * S - head (the combine with the encode
+ * rows where that encoder wants an aligned input); the first and the last
+ * stripe, where the write covers them in part, run one launch of ec_rmw_edge.
+ * Nothing is allocated or uploaded; an old chunk may be the chunk of out[]
+ * that replaces it (head < S, size > 0). */
+int ecd_writev_rmw_device(int device, void *stream, uint32_t k, uint32_t n, uint64_t head,
+                          uint64_t size, const void *user, const void *const *old_head,
+                          const void *const *old_tail, const uint8_t *inv, void *const *out,
+                          const uint8_t *enc_pat);
+
 /* Decode / reconstruct: frags[0..nfrags) are fragment buffers of
  * nstripes*512 bytes (NULL for fragments no pattern reads).  Output: when
  * outs is NULL, out = nstripes*rows*512 bytes, stripe-major (decoded data);

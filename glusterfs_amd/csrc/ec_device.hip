@@ -1903,6 +1903,66 @@ int ecd_readv_decode_device(int device, void *stream, uint32_t k, uint64_t head,
     });
 }
 
+int ecd_writev_rmw_device(int device, void *stream, uint32_t k, uint32_t n, uint64_t head,
+                          uint64_t size, const void *user, const void *const *old_head,
+                          const void *const *old_tail, const uint8_t *inv, void *const *out,
+                          const uint8_t *enc_pat)
+{
+    const uint64_t S = (uint64_t)k * ECD_CHUNK;
+    if (k == 0 || k > ECD_MAX_K || n == 0 || n >= ECD_MAX_ROWS || head >= S || size == 0 ||
+        !user || !out || !enc_pat || ((old_head || old_tail) && !inv))
+        return -EINVAL;
+    /* byte o of stripe t is read at u0 + t * S + o; u0 may lie in front of user */
+    const uintptr_t u0 = (uintptr_t)user - (uintptr_t)head;
+    const uint64_t end = head + size;
+    const uint64_t first_whole = head ? 1 : 0, whole_end = end / S;
+    ecdk_rmw_edge_t edge[2];
+    uint32_t nedges = 0;
+    if (head != 0 || end < S) /* the first stripe, cut at one end or both */
+        edge[nedges++] = {0, end <= S && !old_head ? old_tail : old_head, (uint32_t)head,
+                          (uint32_t)(end < S ? end : S)};
+    if (whole_end >= 1 && end % S != 0) /* another stripe, in which the write ends */
+        edge[nedges++] = {whole_end, old_tail, 0, (uint32_t)(end % S)};
+    return on_device(device, stream, [&](hipStream_t s) {
+        int rc = 0;
+        if (whole_end > first_whole) {
+            /* the stripes that the write covers wholly: ec_method_encode_device's
+             * launch, its input wherever the write puts it */
+            const uint64_t cnt = whole_end - first_whole;
+            const uint8_t *in = reinterpret_cast<const uint8_t *>(u0 + first_whole * S);
+            void *outs[ECD_MAX_ROWS];
+            for (uint32_t i = 0; i < n; ++i)
+                outs[i] = static_cast<uint8_t *>(out[i]) + first_whole * ECD_CHUNK;
+            if (ecdk_has_vander(k, n) &&
+                (((uintptr_t)in & 15u) == 0 || ecdk_encode_any_alignment(k, n))) {
+                rc = ecdk_encode_vander(s, k, n, cnt, in, outs);
+            } else {
+                /* no encoder of its own, or the register encoder (2+1) and an
+                 * input off 16 bytes: the combine with the encode rows */
+                ecd_combine_desc_t d;
+                memset(&d, 0, offsetof(ecd_combine_desc_t, pat));
+                d.k = k;
+                d.rows = n;
+                d.nstripes = cnt;
+                d.npatterns = 1;
+                d.pat_bytes = k + n * k;
+                d.in_stride = S;
+                d.out_stride = ECD_CHUNK;
+                for (uint32_t p = 0; p < k; ++p)
+                    d.in_base[p] = in + (uint64_t)p * ECD_CHUNK;
+                for (uint32_t i = 0; i < n; ++i)
+                    d.out_base[i] = outs[i];
+                memcpy(d.pat, enc_pat, d.pat_bytes);
+                rc = ecdk_combine(s, &d);
+            }
+        }
+        if (rc == 0 && nedges)
+            rc = ecdk_rmw_edge(s, k, n, inv, enc_pat + k, reinterpret_cast<const uint8_t *>(u0),
+                               out, nedges, edge);
+        return rc;
+    });
+}
+
 int ecd_decode_host(int ndev, uint32_t k, uint32_t rows, uint64_t nstripes, uint32_t nfrags,
                     const void *const *frags, void *out, void *const *outs, uint32_t npatterns,
                     const uint8_t *pats, const uint8_t *group_pattern, uint32_t group_shift)

@@ -54,6 +54,23 @@ typedef struct ecdk_clip_edge {
 } ecdk_clip_edge_t;
 int ecdk_decode_clip(hipStream_t s, uint32_t k, const void *const *in, const uint8_t *inv,
                      uint32_t nedges, const ecdk_clip_edge_t *edge);
+/* The partly covered stripes of ecd_writev_rmw_device (ec_rmw_edge): the k
+ * stored chunks old[0 .. k) of stripe t (old null: zeros) are decoded with
+ * inv, bytes [lo, hi) of the stripe's k * 512 are replaced by user0[t * k * 512
+ * + lo ..] and the n chunks of the result go to out[i] + t * 512.  inv: k x k
+ * bytes (not read when no edge has old chunks); enc: n x k bytes, the encode
+ * matrix.  An old chunk may be the chunk of out that replaces it. */
+typedef struct ecdk_rmw_edge {
+    uint64_t t;
+    const void *const *old;
+    uint32_t lo, hi;
+} ecdk_rmw_edge_t;
+int ecdk_rmw_edge(hipStream_t s, uint32_t k, uint32_t n, const uint8_t *inv, const uint8_t *enc,
+                  const uint8_t *user0, void *const *out, uint32_t nedges,
+                  const ecdk_rmw_edge_t *edge);
+/* 1 when ecdk_encode_vander(k, n) reads its input at any byte alignment (the
+ * tile encoders), 0 when it wants 16-byte alignment (the register encoder) */
+int ecdk_encode_any_alignment(uint32_t k, uint32_t n);
 /* the one or two damaged bricks per stripe of ecd_locate2 (ec_locate2_n) */
 int ecdk_locate2(hipStream_t s, const ecd_combine_desc_t *d, const void *const *check,
                  const uint8_t *check_brick, const uint8_t *basis_brick, const uint8_t *ratio,

@@ -1291,6 +1291,70 @@ int ecdk_decode_clip(hipStream_t s, uint32_t k, const void *const *in, const uin
     return launch_ok("launch_decode_clip");
 }
 
+/* ----------------------------------------- ranged write: the edge stripes */
+
+int ecdk_encode_any_alignment(uint32_t k, uint32_t n)
+{
+    return enc_tiles() && ecdk_has_vander(k, n) && k != 2;
+}
+
+/* edge[0 .. nedges): the one or two stripes to merge and encode.  One launch
+ * of one block per edge; the old chunk pointers, inv, the encode matrix, the
+ * fragment pointers and the clips travel in the kernel arguments. */
+int ecdk_rmw_edge(hipStream_t s, uint32_t k, uint32_t n, const uint8_t *inv, const uint8_t *enc,
+                  const uint8_t *user0, void *const *out, uint32_t nedges,
+                  const ecdk_rmw_edge_t *edge)
+{
+    static_assert(sizeof(RmwEdgeArgs) <= 2048, "the tables must fit the kernel arguments");
+    RmwEdgeArgs a;
+    if (k == 0 || k > ECD_MAX_K || n == 0 || n >= ECD_MAX_ROWS || !enc || !out || !edge ||
+        nedges == 0 || nedges > 2)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    a.k = k;
+    a.kw = (k + 3) / 4;
+    a.n = n;
+    a.user = user0;
+    for (u32 i = 0; i < n; ++i) {
+        if (!out[i])
+            return -EINVAL;
+        a.out[i] = static_cast<uint8_t *>(out[i]);
+    }
+    bool any_old = false;
+    for (u32 e = 0; e < nedges; ++e) {
+        if (edge[e].lo >= edge[e].hi || edge[e].hi > k * ECD_CHUNK)
+            return -EINVAL;
+        a.t[e] = edge[e].t;
+        a.lo[e] = edge[e].lo;
+        a.hi[e] = edge[e].hi;
+        if (!edge[e].old)
+            continue;
+        any_old = true;
+        for (u32 p = 0; p < k; ++p) {
+            if (!edge[e].old[p])
+                return -EINVAL;
+            a.old[e * ECD_MAX_K + p] = static_cast<const uint8_t *>(edge[e].old[p]);
+        }
+    }
+    if (any_old) {
+        if (!inv)
+            return -EINVAL;
+        pack_rows(a.inv, 0, k, k, a.kw, inv);
+    }
+    pack_rows(a.enc, 0, n, k, a.kw, enc);
+    /* the old chunks in slot 0 and the merged stripe in slot 1 of one scrub
+     * tile: at most 32 KiB */
+    const size_t lds = scrub_tile_lds(k, 0);
+    /* the k -> K buckets and wave counts of ecdk_decode_clip */
+    if (k <= 4)
+        hipLaunchKernelGGL((ec_rmw_edge<4, 4>), dim3(nedges), dim3(4 * 64), lds, s, a);
+    else if (k <= 8)
+        hipLaunchKernelGGL((ec_rmw_edge<8, 8>), dim3(nedges), dim3(8 * 64), lds, s, a);
+    else
+        hipLaunchKernelGGL((ec_rmw_edge<16, 8>), dim3(nedges), dim3(8 * 64), lds, s, a);
+    return launch_ok("launch_rmw_edge");
+}
+
 /* ------------------------------------------ locating up to two bricks */
 
 /* The arguments of ec_locate2_n from what ecdk_locate2 is given: pack_locate,

@@ -2432,6 +2432,117 @@ __global__ __launch_bounds__(NW * 64) void ec_decode_clip(const DecodeClipArgs a
     }
 }
 
+/* ------------------------------------ ranged write: the edge stripes */
+
+/* Kernel arguments of ec_rmw_edge.  old[e * ECD_MAX_K + p] is the stored chunk
+ * of edge e on the p-th brick of the mask (old[e * ECD_MAX_K] null: the stripe
+ * lies beyond end of file and reads as zeros); inv is inv(mask) and enc the
+ * encode matrix (k and n rows of kw words, a byte per input); out[i] is
+ * fragment i.  user is the address that byte 0 of stripe 0 would have in the
+ * caller's buffer -- `head` bytes in front of it -- so byte o of stripe t[e]
+ * is user[t[e] * S + o], and only the bytes [lo[e], hi[e]) of that stripe are
+ * read there.  1336 bytes. */
+struct RmwEdgeArgs {
+    const uint8_t *old[2 * ECD_MAX_K];
+    uint8_t *out[ECD_MAX_ROWS];
+    const uint8_t *user;
+    uint64_t t[2];
+    u32 lo[2], hi[2];
+    u32 k, kw, n;
+    u32 inv[ECD_MAX_K * ECD_MAX_K / 4];
+    u32 enc[ECD_MAX_ROWS * ECD_MAX_K / 4];
+};
+
+/* ec_method_writev_rmw_device: the one or two stripes that an unaligned write
+ * covers in part.  Block e reads the k stored chunks of stripe t[e], puts the
+ * user bytes [lo[e], hi[e]) over what they decode to and stores the n chunks
+ * of the merged stripe at out[i] + 512 t[e].  The LDS is one scrub tile of k
+ * 2 KiB inputs, as in ec_decode_clip: the old chunks are staged into its
+ * stripe slot 0, and the merged stripe is built in stripe slot 1 of the same
+ * tile, 64 bytes on, which nothing stages into: the chunk layout that
+ * row_product reads, with the same strides.  Lanes 0 .. 15 of a wave hold the
+ * stripe's 16 dword columns.  The other 48 read the same LDS columns as they
+ * (a broadcast: slot 0 before the second barrier, slot 1 after it, so no lane
+ * reads a region that another wave is writing), compute the same products,
+ * and neither load user bytes nor store anything.
+ * Every read of an old chunk is over at the second barrier and every store
+ * comes after it, so an output may be the buffer an old chunk was read from. */
+template <int K, int NW>
+__global__ __launch_bounds__(NW * 64) void ec_rmw_edge(const RmwEdgeArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const bool e = blockIdx.x != 0;
+    const u32 tid = threadIdx.x;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    const u32 k = a.k;
+    const uint64_t t = e ? a.t[1] : a.t[0];
+    const u32 lo = e ? a.lo[1] : a.lo[0], hi = e ? a.hi[1] : a.hi[0];
+    const u32 eo = e ? (u32)ECD_MAX_K : 0u;
+    const bool has_old = a.old[eo] != nullptr;
+    uint8_t *merged = lds + 64u;
+    if (has_old)
+        stage_tile<kScrubT, NW>(lds, [&](u32 p, uint64_t) -> const uint8_t * {
+            return a.old[eo + p];
+        }, k, 0, 1, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    /* the user bytes of this stripe, which lanes 0 .. 15 alone load */
+    const uint8_t *us = a.user + t * ((uint64_t)k * ECD_CHUNK);
+    for (u32 j = wave; j < k; j += NW) {
+        const u32 r0 = j * ECD_CHUNK;
+        u32 d[8][1];
+        if (lo <= r0 && r0 + ECD_CHUNK <= hi) {
+            /* the write covers the row: user bytes alone, at any alignment */
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                d[b][0] = 0;
+            if (cs == 0) {
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    __builtin_memcpy(&d[b][0], us + r0 + (u32)b * 64u + cc * 4u, 4);
+            }
+        } else {
+            if (has_old) {
+                row_product<K>(a.inv, j, a.kw, k, lds + cc * 4u, d);
+            } else {
+#pragma unroll
+                for (int b = 0; b < 8; ++b)
+                    d[b][0] = 0;
+            }
+            if (cs == 0 && r0 < hi && lo < r0 + ECD_CHUNK) {
+                /* the clip cuts the row: the user bytes inside it, byte by
+                 * byte.  Every load is issued, from an offset clamped into
+                 * the clip, so none waits for a branch or another load. */
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    const u32 o = r0 + (u32)b * 64u + cc * 4u;
+#pragma unroll
+                    for (u32 i = 0; i < 4; ++i) {
+                        const u32 at = o + i < lo ? lo : (o + i >= hi ? hi - 1u : o + i);
+                        const u32 v = us[at];
+                        if (at == o + i)
+                            d[b][0] = (d[b][0] & ~(0xFFu << (8u * i))) | (v << (8u * i));
+                    }
+                }
+            }
+        }
+        if (cs == 0) {
+#pragma unroll
+            for (int b = 0; b < 8; ++b)
+                *reinterpret_cast<u32 *>(merged + j * kScrubSlot + (u32)b * (kScrubT * 64u) +
+                                         cc * 4u) = d[b][0];
+        }
+    }
+    __syncthreads();
+    for (u32 i = wave; i < a.n; i += NW) {
+        u32 acc[8][1];
+        row_product<K>(a.enc, i, a.kw, k, merged + cc * 4u, acc);
+        if (cs == 0)
+            store_chunk<1, false>(a.out[i] + t * ECD_CHUNK + cc * 4u, acc);
+    }
+}
+
 /* ------------------------------------------- repairing the named chunks */
 
 /* Kernel arguments of ec_repair_n.  frag[] is indexed by brick (null outside

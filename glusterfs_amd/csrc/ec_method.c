@@ -4245,6 +4245,187 @@ ecm_readv_decode_device_impl(ec_matrix_list_t *list, int device, void *stream, u
     return ecd_readv_decode_device(device, stream, k, head, size, in, pat + k, dst);
 }
 
+/* ------------------------------------- unaligned writes over stored fragments */
+
+/* Weak like ecd_readv_decode_device: without the symbol
+ * ec_method_writev_rmw_device is -ENODEV. */
+extern __typeof__(ecd_writev_rmw_device) ecd_writev_rmw_device __attribute__((weak));
+
+/* an argument error of the ranged write, with its reason for
+ * ec_method_last_error() */
+static int
+rmw_inval(const char *why)
+{
+    char buf[160];
+
+    snprintf(buf, sizeof buf, "ec_method_writev_rmw: %s", why);
+    ecd_set_error(buf);
+    return -EINVAL;
+}
+
+/* What both entry points check first: the list, the n outputs, a write that
+ * starts inside its first stripe and, when an old array is given, its k
+ * chunks and the mask.  pat then gets the pattern of ec_method_decode_device
+ * (input p is the p-th brick of the mask, the coefficients are inv(mask) from
+ * the list's cache); with both arrays NULL the mask is ignored and pat is not
+ * written. */
+static int
+rmw_args(ec_matrix_list_t *list, uint64_t head, uintptr_t mask, const void *const *old_head,
+         const void *const *old_tail, void *const *out, uint8_t *pat)
+{
+    uint32_t rows[ECM_MAX_K], k, p;
+    uint8_t src[ECM_MAX_K];
+    ecm_matrix_t *m;
+
+    if (!list || !CTX(list))
+        return rmw_inval("no list");
+    if (!out)
+        return rmw_inval("no output list");
+    for (p = 0; p < list->rows; p++)
+        if (!out[p])
+            return rmw_inval("an output is NULL");
+    k = list->columns;
+    if (head >= (uint64_t)k * EC_METHOD_CHUNK_SIZE)
+        return rmw_inval("head is not inside the first stripe");
+    if (!old_head && !old_tail)
+        return 0;
+    /* rows_from_mask writes a row for every bit: count them first */
+    if (popcount_mask(mask) != k)
+        return rmw_inval("the mask is not k bricks of the volume");
+    rows_from_mask(mask, rows);
+    if (!mask_rows_ok(list, mask, rows))
+        return rmw_inval("the mask is not k bricks of the volume");
+    for (p = 0; p < k; p++) {
+        if ((old_head && !old_head[p]) || (old_tail && !old_tail[p]))
+            return rmw_inval("an old chunk is NULL");
+        src[p] = (uint8_t)p;
+    }
+    m = matrix_get(list, mask, rows);
+    if (!m)
+        return -ENOMEM;
+    pack_pattern(pat, k, src, k, m->inv);
+    matrix_put(list, m);
+    return 0;
+}
+
+/* The byte-exact specification of the ranged write, on the calling thread's
+ * CPU engine.  Both edge stripes are decoded into hbuf and tbuf before any
+ * output is written, so an old chunk may be the chunk of out[] that replaces
+ * it; then the gather encoder codes the virtual input -- the old bytes in
+ * front of the write, the segments in order, the old bytes behind it -- and
+ * copies only the stripes that a boundary between two of them cuts. */
+static int32_t
+ecm_writev_rmw_impl(ec_matrix_list_t *list, uint64_t head, const struct iovec *iov, int count,
+                    uintptr_t mask, const void *const *old_head, const void *const *old_tail,
+                    void *const *out)
+{
+    uint8_t hbuf[ECM_MAX_K * EC_METHOD_CHUNK_SIZE], tbuf[ECM_MAX_K * EC_METHOD_CHUNK_SIZE];
+    const void *seg_stack[2 + 64], **segp = seg_stack;
+    uint64_t len_stack[2 + 64], *segl = len_stack;
+    const void *const *olds[2];
+    const uint8_t *hs = NULL, *ts = NULL;
+    uint8_t *bufs[2] = {hbuf, tbuf};
+    ecd_combine_desc_t d;
+    uint64_t size = 0, S, end, ns;
+    uint32_t k, n, p, e, nsegs = 0;
+    int c, rc;
+
+    if (count < 0)
+        return rmw_inval("count is negative");
+    if (count > 0 && !iov)
+        return rmw_inval("no segment list");
+    rc = rmw_args(list, head, mask, old_head, old_tail, out, d.pat);
+    if (rc)
+        return rc;
+    for (c = 0; c < count; c++) {
+        if (iov[c].iov_len && !iov[c].iov_base)
+            return rmw_inval("a segment is NULL");
+        size += iov[c].iov_len;
+    }
+    if (size == 0)
+        return 0;
+    k = list->columns;
+    n = list->rows;
+    for (c = 0; c < count; c++)
+        if (iov[c].iov_len && ecd_ptr_device(iov[c].iov_base) >= 0)
+            return rmw_inval("a segment is device memory");
+    if ((old_head && !bufs_on(old_head, k, -1)) || (old_tail && !bufs_on(old_tail, k, -1)))
+        return rmw_inval("an old chunk is device memory");
+    if (!bufs_on((const void *const *)out, n, -1))
+        return rmw_inval("an output is device memory");
+    S = (uint64_t)k * EC_METHOD_CHUNK_SIZE;
+    end = head + size;
+    ns = (end + S - 1) / S;
+    /* the edges: the first stripe where the write cuts it (one stripe: its old
+     * content is either array), and another stripe in which the write ends */
+    olds[0] = head != 0 || end < S ? (ns == 1 && !old_head ? old_tail : old_head) : NULL;
+    olds[1] = ns > 1 && end % S != 0 ? old_tail : NULL;
+    desc_init(&d, k, k, 1, EC_METHOD_CHUNK_SIZE, S);
+    for (e = 0; e < 2; e++) {
+        if (!olds[e])
+            continue;
+        for (p = 0; p < k; p++) {
+            d.in_base[p] = olds[e][p];
+            d.out_base[p] = bufs[e] + (size_t)p * EC_METHOD_CHUNK_SIZE;
+        }
+        rc = ecc_combine(CTX(list)->isa, &d);
+        if (rc)
+            return rc;
+    }
+    if (olds[0])
+        hs = hbuf;
+    if (ns == 1)
+        ts = hs ? hbuf + end : NULL;
+    else if (olds[1])
+        ts = tbuf + end % S;
+    if (count > 64) {
+        segp = (const void **)malloc((size_t)(count + 2) * (sizeof(*segp) + sizeof(*segl)));
+        if (!segp)
+            return -ENOMEM;
+        segl = (uint64_t *)(segp + count + 2);
+    }
+    segp[nsegs] = hs;
+    segl[nsegs++] = head;
+    for (c = 0; c < count; c++) {
+        segp[nsegs] = iov[c].iov_base;
+        segl[nsegs++] = iov[c].iov_len;
+    }
+    segp[nsegs] = ts;
+    segl[nsegs++] = ns * S - end;
+    rc = ecc_encode_gather(CTX(list)->isa, k, n, ns, nsegs, segp, segl, (uint8_t *const *)out);
+    if (segp != seg_stack)
+        free(segp);
+    return rc;
+}
+
+static int32_t
+ecm_writev_rmw_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t head,
+                           uint64_t size, const void *user, uintptr_t mask,
+                           const void *const *old_head, const void *const *old_tail,
+                           void *const *out)
+{
+    uint8_t pat[ECM_MAX_K + ECM_MAX_K * ECM_MAX_K];
+    uint32_t k;
+    int rc;
+
+    rc = rmw_args(list, head, mask, old_head, old_tail, out, pat);
+    if (rc)
+        return rc;
+    if (size == 0)
+        return 0;
+    if (!user)
+        return rmw_inval("no user bytes");
+    if (!ecd_writev_rmw_device)
+        return -ENODEV;
+    k = list->columns;
+    if (!scrub_on_device(device, old_head, old_head ? k : 0, old_tail, old_tail ? k : 0, out,
+                         list->rows, user, NULL))
+        return rmw_inval("a buffer is not memory of the device");
+    return ecd_writev_rmw_device(device, stream, k, list->rows, head, size, user, old_head,
+                                 old_tail, old_head || old_tail ? pat + k : NULL, out,
+                                 CTX(list)->enc_pat);
+}
+
 /* ---------------------------------------------------- device-resident */
 
 static int32_t
@@ -4767,6 +4948,28 @@ ec_method_readv_decode_device(ec_matrix_list_t *list, int device, void *stream, 
     return ecm_ret("ec_method_readv_decode_device", seq,
                    ecm_readv_decode_device_impl(list, device, stream, head, size, mask, in,
                                                 dst));
+}
+
+int32_t
+ec_method_writev_rmw(ec_matrix_list_t *list, uint64_t head, const struct iovec *iov, int count,
+                     uintptr_t mask, const void *const *old_head, const void *const *old_tail,
+                     void *const *out)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_writev_rmw", seq,
+                   ecm_writev_rmw_impl(list, head, iov, count, mask, old_head, old_tail, out));
+}
+
+int32_t
+ec_method_writev_rmw_device(ec_matrix_list_t *list, int device, void *stream, uint64_t head,
+                            uint64_t size, const void *user, uintptr_t mask,
+                            const void *const *old_head, const void *const *old_tail,
+                            void *const *out)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_writev_rmw_device", seq,
+                   ecm_writev_rmw_device_impl(list, device, stream, head, size, user, mask,
+                                              old_head, old_tail, out));
 }
 
 int32_t

@@ -65,6 +65,7 @@ EXPORTS = (
     "ec_method_heal_verified", "ec_method_heal_verified_device",
     "ec_method_scrub_report", "ec_method_scrub_report_device", "ec_method_scrub_report_work",
     "ec_method_readv_decode", "ec_method_readv_decode_device",
+    "ec_method_writev_rmw", "ec_method_writev_rmw_device",
 )
 
 
@@ -248,6 +249,9 @@ def _load():
                                                  vp]),
         "ec_method_readv_decode": (i32, [P, u64, up, vp, vp, ctypes.c_int]),
         "ec_method_readv_decode_device": (i32, [P, ctypes.c_int, vp, u64, u64, up, vp, vp]),
+        "ec_method_writev_rmw": (i32, [P, u64, vp, ctypes.c_int, up, vp, vp, vp]),
+        "ec_method_writev_rmw_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, up, vp, vp,
+                                              vp]),
         "ec_method_config_fill": (None, [u32, u32, ctypes.POINTER(Config)]),
         "ec_method_config_pack": (i32, [ctypes.POINTER(Config), vp]),
         "ec_method_config_unpack": (i32, [vp, ctypes.c_size_t, ctypes.POINTER(Config)]),
@@ -587,6 +591,27 @@ class ECMatrixList:
         return _check(lib.ec_method_readv_decode_device(
             ctypes.byref(self._list), device, stream, head, size, mask, _ptr_array(inp),
             addr(out)), "ec_method_readv_decode_device")
+
+    def writev_rmw(self, head, user, mask, old_head, old_tail, out):
+        """ec_method_writev_rmw: `user` is one buffer or a list of buffers (the
+        writev iovec list); old_head / old_tail are lists of the k stored
+        chunks of the first / last stripe, or None."""
+        bufs = user if isinstance(user, (list, tuple)) else [user]
+        iov = (_IOVec * len(bufs))(*[_IOVec(addr(b), _nbytes(b)) for b in bufs])
+        return _check(lib.ec_method_writev_rmw(
+            ctypes.byref(self._list), head, iov, len(bufs), mask,
+            None if old_head is None else _ptr_array(old_head),
+            None if old_tail is None else _ptr_array(old_tail), _ptr_array(out)),
+            "ec_method_writev_rmw")
+
+    def writev_rmw_device(self, device, stream, head, size, user, mask, old_head, old_tail,
+                          out):
+        """ec_method_writev_rmw_device: `user` gives exactly `size` bytes."""
+        return _check(lib.ec_method_writev_rmw_device(
+            ctypes.byref(self._list), device, stream, head, size, addr(user), mask,
+            None if old_head is None else _ptr_array(old_head),
+            None if old_tail is None else _ptr_array(old_tail), _ptr_array(out)),
+            "ec_method_writev_rmw_device")
 
     def heal(self, nstripes, mask, inp, target_mask, out):
         return _check(lib.ec_method_heal(ctypes.byref(self._list), nstripes, mask,

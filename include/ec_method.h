@@ -814,6 +814,87 @@ int32_t ec_method_writev_encode(ec_matrix_list_t *list, uint64_t head, const str
 int32_t ec_method_readv_decode(ec_matrix_list_t *list, uint64_t head, uintptr_t mask,
                                const void *const *in, const struct iovec *iov, int count);
 
+/* Write of an unaligned byte range over stored fragments: the partial-stripe
+ * write above for a caller that holds no decoded stripes.  ec_writev_start
+ * takes the old content of the first and the last stripe from the stripe
+ * cache or from an ec_readv (ec-inode-write.c:1987-2085); a caller that keeps
+ * a file as fragments, in device memory above all, holds the stored chunks
+ * and would decode each edge stripe into a temporary before
+ * ec_method_writev_encode.  These calls take the old chunks as they are
+ * stored, from any k bricks, decode what the write does not cover, merge and
+ * encode in one pass, and may write the result over the chunks they read.
+ *
+ * S = 512 * k is the stripe.  head < S is the offset of the first user byte
+ * inside its stripe (fop->head); size is the sum of the iov_len (host
+ * variant) or the argument (device variant); end = head + size and ns =
+ * ceil(end / S) stripes are written.  mask has exactly k bits below n, the
+ * numbering of every decode mask.  old_head[p] is 512 bytes, the stored chunk
+ * of the write's first stripe on the brick of the p-th set bit of mask, and
+ * old_tail[p] the same for the last stripe.  Either array may be NULL: the
+ * stripe then lies beyond end of file and reads as zeros (:2007-2008).  When
+ * ns == 1 the stripe's old content is old_head, or old_tail when old_head is
+ * NULL, the rule of ec_method_writev_encode.
+ *
+ * The first stripe, when head != 0 or end < S, is O0 -- the S bytes that
+ * ec_method_decode gives for old_head and mask, or zeros -- with bytes [head,
+ * min(end, S)) replaced by user bytes.  The last stripe, when ns > 1 and end %
+ * S != 0, is O1 (from old_tail) with bytes [0, end % S) replaced.  Every other
+ * stripe is user bytes alone.  out[i], i < n, indexed by brick, receives ns
+ * chunks of fragment i, the encode of those ns * S bytes: byte for byte what
+ * ec_method_writev_encode gives when handed the decoded O0 and O1.  out[] is
+ * not modified.
+ *
+ * An old array is read only if its stripe is an edge in the sense above; each
+ * old_*[p] is read for exactly 512 bytes and never written through that
+ * pointer; nothing is written outside [out[i], out[i] + ns * 512).  The host
+ * variant reads exactly the iov_len bytes of each segment.  The device variant
+ * reads no byte of user outside the aligned dwords that hold the size bytes:
+ * where the stripes that the write covers wholly do not start on a dword, the
+ * encoder loads the dwords that cover them, as ec_method_writev_encode_device
+ * does, so up to 3 bytes on either side, never another page; the edge stripes
+ * read the user bytes alone.  user, every old_*[p] and every out[i] may have
+ * any byte alignment.  n <= 31 (EC_MI355X_MAX_NODES), which ec_method_init
+ * enforces for every list.
+ *
+ * In place: for a brick b in mask at position p, old_head[p] == out[b] is
+ * allowed, and so is old_tail[p] == out[b] + (ns - 1) * 512 (with ns == 1 that
+ * is old_tail[p] == out[b]): the stored chunk is then replaced by the new one.
+ * Any other overlap between an old chunk and an output range, or between user
+ * bytes and an output range, is undefined.
+ *
+ * mask is checked when either old array is non-NULL; with both NULL it is
+ * ignored.  size == 0 returns 0 after the argument checks and writes nothing.
+ * head == 0 with size % S == 0 reads no old chunk and is byte for byte
+ * ec_method_encode_device (or _batch) of the user bytes.
+ *
+ * -EINVAL: a NULL list, out, out[i] (i < n), or user / iov with bytes to
+ * write; count < 0; a NULL iov_base with a non-zero length; head >= S; an old
+ * array given with a mask that is not exactly k bricks below n; a NULL entry
+ * in an old array that is given; host and device buffers mixed, or given to
+ * the wrong entry point.  Each leaves its reason in ec_method_last_error().
+ * -ENODEV where the device layer lacks the call.
+ *
+ * The device variant is asynchronous on `stream` with no host
+ * synchronisation.  It allocates nothing and uploads nothing -- the old chunk
+ * pointers, inv(mask), the encode matrix and the clips travel in the kernel
+ * arguments -- pre-zeroes nothing, uses no global atomics and issues at most
+ * two launches: the encoder of ec_method_encode_device for the stripes that
+ * the write covers wholly, its input at user + t * S - head, and one small
+ * kernel for the first and the last stripe where the write covers them in
+ * part.
+ *
+ * The host variant runs on the calling thread's CPU engine whatever the
+ * volume's engine is; like ec_method_readv_decode it leaves
+ * ec_method_stats_t, the router and the run-time compiler alone.  It decodes
+ * both edge stripes into S-byte buffers on the stack before it writes any
+ * output, then encodes the old head bytes, the segments in order (segments of
+ * length 0 are allowed) and the old tail bytes with the CPU engine's gather
+ * encoder; no interior byte is copied.  It is the byte-exact specification
+ * and what runs without a GPU. */
+int32_t ec_method_writev_rmw(ec_matrix_list_t *list, uint64_t head, const struct iovec *iov,
+                             int count, uintptr_t mask, const void *const *old_head,
+                             const void *const *old_tail, void *const *out);
+
 /* Device-resident, asynchronous variants for callers that keep stripes in
  * MI355X memory: all buffers are device pointers on `device` (index among
  * the visible gfx950 devices), work is queued on `stream` (a hipStream_t;
@@ -852,6 +933,11 @@ int32_t ec_method_writev_encode_device(ec_matrix_list_t *list, int device, void 
 int32_t ec_method_readv_decode_device(ec_matrix_list_t *list, int device, void *stream,
                                       uint64_t head, uint64_t size, uintptr_t mask,
                                       const void *const *in, void *dst);
+/* the unaligned write above on device buffers: user gives exactly size bytes */
+int32_t ec_method_writev_rmw_device(ec_matrix_list_t *list, int device, void *stream,
+                                    uint64_t head, uint64_t size, const void *user,
+                                    uintptr_t mask, const void *const *old_head,
+                                    const void *const *old_tail, void *const *out);
 int32_t ec_method_sync_device(int device, void *stream);
 
 /* ------------------------------------------------------------------------
