@@ -266,6 +266,22 @@ int ecd_writev_rmw_device(int device, void *stream, uint32_t k, uint32_t n, uint
                           const void *const *old_tail, const uint8_t *inv, void *const *out,
                           const uint8_t *enc_pat);
 
+/* Fused heal with per-group patterns, on device memory (asynchronous on
+ * `stream`; ec_method_heal_mixed_device): frags[0 .. ECD_MAX_ROWS) is indexed
+ * by brick (NULL for a brick that no pattern with targets names), nstripes *
+ * 512 bytes each.  Stripe group g of 1 << group_shift stripes (>= 4) uses
+ * pattern group_pattern[g] (device memory; ids >= npatterns clamp to the last
+ * pattern).  pats (host memory, read during the call): npatterns packed
+ * patterns of k + 1 + mmax + mmax * k bytes -- src[k], m, dst[mmax],
+ * coef[mmax][k] with m <= mmax < 16.  For every stripe t of a group whose
+ * pattern has m > 0 and every j < m, chunk t of frags[dst[j]] becomes the sum
+ * over p of coef[j][p] * chunk t of frags[src[p]]; nothing else is written,
+ * and a group with m == 0 is not read.  One launch of ec_heal_mixed_n; pattern
+ * sets beyond its kernel arguments go to a table of the pattern cache. */
+int ecd_heal_mixed(int device, void *stream, uint32_t k, uint64_t nstripes,
+                   const uint8_t *group_pattern, uint32_t group_shift, uint32_t npatterns,
+                   uint32_t mmax, const uint8_t *pats, void *const *frags);
+
 /* Decode / reconstruct: frags[0..nfrags) are fragment buffers of
  * nstripes*512 bytes (NULL for fragments no pattern reads).  Output: when
  * outs is NULL, out = nstripes*rows*512 bytes, stripe-major (decoded data);

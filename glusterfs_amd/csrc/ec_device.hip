@@ -1963,6 +1963,16 @@ int ecd_writev_rmw_device(int device, void *stream, uint32_t k, uint32_t n, uint
     });
 }
 
+int ecd_heal_mixed(int device, void *stream, uint32_t k, uint64_t nstripes,
+                   const uint8_t *group_pattern, uint32_t group_shift, uint32_t npatterns,
+                   uint32_t mmax, const uint8_t *pats, void *const *frags)
+{
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_heal_mixed(s, k, nstripes, group_pattern, group_shift, npatterns, mmax, pats,
+                               frags);
+    });
+}
+
 int ecd_decode_host(int ndev, uint32_t k, uint32_t rows, uint64_t nstripes, uint32_t nfrags,
                     const void *const *frags, void *out, void *const *outs, uint32_t npatterns,
                     const uint8_t *pats, const uint8_t *group_pattern, uint32_t group_shift)

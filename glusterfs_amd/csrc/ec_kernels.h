@@ -68,6 +68,17 @@ typedef struct ecdk_rmw_edge {
 int ecdk_rmw_edge(hipStream_t s, uint32_t k, uint32_t n, const uint8_t *inv, const uint8_t *enc,
                   const uint8_t *user0, void *const *out, uint32_t nedges,
                   const ecdk_rmw_edge_t *edge);
+/* The fused heal with per-group patterns of ecd_heal_mixed (ec_heal_mixed_n):
+ * stripe group g of 1 << group_shift stripes (>= 4) uses pattern
+ * group_pattern[g], ids past the last clamped to it.  pats: npatterns packed
+ * patterns of k + 1 + mmax + mmax * k bytes each -- src[k], m, dst[mmax],
+ * coef[mmax][k], of which a pattern uses its m <= mmax < 16 first targets and
+ * rows; frags: ECD_MAX_ROWS pointers indexed by brick.  For every stripe t of
+ * a group with m > 0, chunk t of frags[dst[j]] = XOR_p coef[j][p] * chunk t of
+ * frags[src[p]]. */
+int ecdk_heal_mixed(hipStream_t s, uint32_t k, uint64_t nstripes, const uint8_t *group_pattern,
+                    uint32_t group_shift, uint32_t npatterns, uint32_t mmax, const uint8_t *pats,
+                    void *const *frags);
 /* 1 when ecdk_encode_vander(k, n) reads its input at any byte alignment (the
  * tile encoders), 0 when it wants 16-byte alignment (the register encoder) */
 int ecdk_encode_any_alignment(uint32_t k, uint32_t n);

@@ -1249,6 +1249,119 @@ int ecdk_heal_verified(hipStream_t s, const ecd_combine_desc_t *d, const void *c
     });
 }
 
+/* ------------------------------------- fused heal with per-group patterns */
+
+namespace {
+
+/* the instantiation of ec_heal_mixed_n for k, where the patterns are and the
+ * staging policy: the K buckets and wave counts of ecdk_decode_clip */
+template <bool PG, int LA>
+int launch_heal_mixed(hipStream_t s, const HealMixedArgs &a, u32 g)
+{
+    const size_t lds = scrub_tile_lds(a.k, 0);
+    if (a.k <= 4)
+        hipLaunchKernelGGL((ec_heal_mixed_n<4, 4, PG, LA>), dim3(g), dim3(4 * 64), lds, s, a);
+    else if (a.k <= 8)
+        hipLaunchKernelGGL((ec_heal_mixed_n<8, 8, PG, LA>), dim3(g), dim3(8 * 64), lds, s, a);
+    else
+        hipLaunchKernelGGL((ec_heal_mixed_n<16, 8, PG, LA>), dim3(g), dim3(8 * 64), lds, s, a);
+    return launch_ok("launch_heal_mixed");
+}
+
+} // namespace
+
+/* pats: npatterns packed patterns of k + 1 + mmax + mmax * k bytes each:
+ * src[k], m, dst[mmax], coef[mmax][k] (m <= mmax rows used).  frags: 32
+ * pointers indexed by brick.  One launch; the patterns travel in the kernel
+ * arguments when they fit and in a table of the pattern cache when not. */
+int ecdk_heal_mixed(hipStream_t s, uint32_t k, uint64_t nstripes, const uint8_t *group_pattern,
+                    uint32_t group_shift, uint32_t npatterns, uint32_t mmax, const uint8_t *pats,
+                    void *const *frags)
+{
+    static_assert(sizeof(HealMixedArgs) <= 2048, "the arguments keep to 2 KiB");
+    static_assert(offsetof(HealMixedArgs, pat) == 304, "the header the tests count");
+    HealMixedArgs a;
+    if (k == 0 || k > ECD_MAX_K || !group_pattern || group_shift < 2 || group_shift > 40 ||
+        npatterns == 0 || npatterns > ECD_MAX_PATTERNS || mmax >= 16 || !pats || !frags)
+        return -EINVAL;
+    const uint64_t g = (nstripes + kScrubT - 1) / kScrubT;
+    if (g == 0 || mmax == 0)
+        return 0;               /* no stripe, or no pattern with a target */
+    if (g > 0x7fffffffull)
+        return -EINVAL;
+    memset(&a, 0, sizeof(a));
+    a.k = k;
+    a.kw = (k + 3) / 4;
+    a.nstripes = nstripes;
+    a.group_pattern = group_pattern;
+    a.group_shift = group_shift;
+    a.npatterns = npatterns;
+    a.dw = (mmax + 3) / 4;
+    a.pwords = a.kw + 1 + a.dw + mmax * a.kw;
+    uintptr_t align = 0;
+    for (u32 i = 0; i < ECD_MAX_ROWS; ++i) {
+        a.frag[i] = static_cast<uint8_t *>(frags[i]);
+        align |= (uintptr_t)frags[i];
+    }
+    const size_t pbytes = (size_t)k + 1 + mmax + (size_t)mmax * k;
+    const size_t nw = (size_t)a.pwords * npatterns;
+    const bool pg = nw > (size_t)kHealMixedPatWords;
+    std::vector<u32> table(pg ? nw : 0, 0u);
+    u32 *words = pg ? table.data() : a.pat;
+    for (u32 q = 0; q < npatterns; ++q) {
+        const uint8_t *src = pats + q * pbytes;
+        uint8_t *dst = reinterpret_cast<uint8_t *>(words + (size_t)q * a.pwords);
+        const u32 m = src[k];
+        if (m > mmax)
+            return -EINVAL;
+        for (u32 p = 0; p < k; ++p)
+            if (src[p] >= ECD_MAX_ROWS || (m && !frags[src[p]]))
+                return -EINVAL;
+        memcpy(dst, src, k);
+        dst[4 * a.kw] = (uint8_t)m;
+        for (u32 j = 0; j < m; ++j) {
+            if (src[k + 1 + j] >= ECD_MAX_ROWS || !frags[src[k + 1 + j]])
+                return -EINVAL;
+            dst[4 * (a.kw + 1) + j] = src[k + 1 + j];
+            memcpy(dst + 4 * (a.kw + 1 + a.dw + (size_t)j * a.kw), src + k + 1 + mmax + j * k, k);
+        }
+    }
+    u32 *tab = nullptr;
+    PatTableCache::Ref ref;
+    int rc = 0;
+    if (pg) {
+        rc = pat_tables().acquire(s, table, ref);
+        if (rc == 0) {
+            a.patg = ref.ptr;
+        } else if (rc == -EBUSY) {
+            /* every cache entry in use: a table of this call's own */
+            if (const hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&tab), nw * 4, s)) {
+                (void)hip_ok(e, "hipMallocAsync(per-call pattern table)");
+                return -ENOMEM;
+            }
+            a.patg = tab;
+            rc = enqueue_upload(s, table, tab);
+        }
+    }
+    if (rc == 0) {
+        /* the staging policy of launch_scrub_tile, by the bytes the call reads */
+        const bool nt = nt_staging(nstripes * k * ECD_CHUNK) && (align & 15u) == 0;
+        if (pg)
+            rc = nt ? launch_heal_mixed<true, kLdsDmaNT>(s, a, (u32)g)
+                    : launch_heal_mixed<true, kLdsDmaDefault>(s, a, (u32)g);
+        else
+            rc = nt ? launch_heal_mixed<false, kLdsDmaNT>(s, a, (u32)g)
+                    : launch_heal_mixed<false, kLdsDmaDefault>(s, a, (u32)g);
+    }
+    if (ref.slot >= 0)
+        (void)pat_tables().release(ref, s);   /* a failure drained s: the call stands */
+    if (tab) {
+        const int frc = hip_ok(hipFreeAsync(tab, s), "hipFreeAsync(per-call pattern table)");
+        rc = rc ? rc : frc;
+    }
+    return rc;
+}
+
 /* ------------------------------------------- ranged read: the edge stripes */
 
 /* in: the k fragments (device memory, any byte alignment); inv: k x k bytes,

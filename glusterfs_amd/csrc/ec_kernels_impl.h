@@ -2358,6 +2358,106 @@ __global__ __launch_bounds__(NW * 64) void ec_heal_verified_n(const HealVerified
         a.bad[t.t0 + t.tid] = t.flags[t.tid];
 }
 
+/* ------------------------------------- fused heal with per-group patterns */
+
+/* Kernel arguments of ec_heal_mixed_n.  frag[] is indexed by brick (null for a
+ * brick that no pattern with targets reads or writes).  A pattern is pwords
+ * words:
+ *   [0, kw)               the k source brick indices, a byte each
+ *   [kw]                  m, the number of targets (0: the tile is left alone)
+ *   [kw + 1, kw + 1 + dw) the m target brick indices, a byte each
+ *   then m rows of kw words: row j of the heal matrix E_target * inv(mask), a
+ *   byte per source, as row_product reads it
+ * with dw = ceil(mmax / 4) and pwords = kw + 1 + dw + mmax * kw for the largest
+ * m of the call.  The patterns stand in pat[] (PG = false) or, when they do
+ * not fit, in the device table patg (PG = true); either way every word is read
+ * by a scalar load.  304 bytes in front of pat[], 2,048 in all. */
+constexpr int kHealMixedPatWords = 436;
+
+struct HealMixedArgs {
+    uint8_t *frag[ECD_MAX_ROWS];
+    uint64_t nstripes;
+    const uint8_t *group_pattern;
+    const u32 *patg;
+    u32 k, kw, group_shift, npatterns, pwords, dw;
+    u32 pat[kHealMixedPatWords];
+};
+
+/* word `idx` of the pattern tables (the argument struct is passed in, not
+ * held, as in PatWords) */
+template <bool PG>
+__device__ __forceinline__ u32 heal_mixed_word(const HealMixedArgs &a, u32 idx)
+{
+    if constexpr (PG)
+        return scalar_load_u32(a.patg + idx);
+    else
+        return a.pat[idx];
+}
+
+/* ec_method_heal_mixed_device: the fused heal of ec_heal_verified_n without
+ * the check rows, with the pattern -- sources, targets and heal matrix -- of
+ * the tile's stripe group.  A group is a power of two of at least kScrubT
+ * stripes, so a tile has one pattern: its id is the group's byte of
+ * group_pattern, read and clamped as tile_pattern does.  A pattern without
+ * targets returns before any load.  Otherwise the k source chunks frag[src[p]]
+ * + st * 512 are staged into k tile slots (k * 2 KiB of LDS, no flag words),
+ * the m rows are spread over the waves as in scrub_heal, and row j leaves by
+ * dword stores to frag[dst[j]] for the stripes that exist.  Sources are only
+ * read and a target is none of its pattern's sources, and a tile's stripes
+ * are no other tile's, so the call works in place. */
+template <int K, int NW, bool PG, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_heal_mixed_n(const HealMixedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 tid = threadIdx.x;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    const uint64_t t0 = (uint64_t)blockIdx.x * kScrubT;
+    const u32 k = a.k, kw = a.kw;
+    /* the aligned dword holding the group's byte, by a scalar load */
+    const uintptr_t ba = (uintptr_t)(a.group_pattern + (t0 >> a.group_shift));
+    const u32 gw = scalar_load_u32(reinterpret_cast<const void *>(ba & ~(uintptr_t)3));
+    const u32 id = (gw >> ((u32)(ba & 3u) * 8u)) & 0xFFu;
+    const u32 pb = (id < a.npatterns ? id : a.npatterns - 1u) * a.pwords;
+    const u32 m = __builtin_amdgcn_readfirstlane(heal_mixed_word<PG>(a, pb + kw));
+    if (m == 0)
+        return;
+    /* the src[] words (K / 4 >= kw of them; the pattern has kw + 1 or more) */
+    const u32 s0 = heal_mixed_word<PG>(a, pb);
+    const u32 s1 = K > 4 ? heal_mixed_word<PG>(a, pb + 1) : 0u;
+    const u32 s2 = K > 8 ? heal_mixed_word<PG>(a, pb + 2) : 0u;
+    const u32 s3 = K > 8 ? heal_mixed_word<PG>(a, pb + 3) : 0u;
+    stage_tile<kScrubT, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        /* branch-free pick of the word, as PatWords::byte */
+        const u32 q = p >> 2;
+        const u32 w = (s0 & (0u - (u32)(q == 0))) | (s1 & (0u - (u32)(q == 1))) |
+                      (s2 & (0u - (u32)(q == 2))) | (s3 & (0u - (u32)(q == 3)));
+        const u32 b = __builtin_amdgcn_readfirstlane((w >> ((p & 3u) * 8u)) & (ECD_MAX_ROWS - 1u));
+        return a.frag[b] + st * ECD_CHUNK;
+    }, k, t0, a.nstripes, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    const uint8_t *col = lds + cs * 64u + cc * 4u;
+    const bool live = t0 + cs < a.nstripes;
+    const uint64_t o = (t0 + cs) * (uint64_t)ECD_CHUNK + cc * 4u;
+    const u32 rows = pb + kw + 1u + a.dw;
+    for (u32 j = wave; j < m; j += NW) {
+        const u32 rj = rows + j * kw;
+        u32 row[4];
+        row[0] = heal_mixed_word<PG>(a, rj);
+        row[1] = K > 4 ? heal_mixed_word<PG>(a, rj + 1) : 0u;
+        row[2] = K > 8 ? heal_mixed_word<PG>(a, rj + 2) : 0u;
+        row[3] = K > 8 && kw > 3 ? heal_mixed_word<PG>(a, rj + 3) : 0u;
+        const u32 dwd = heal_mixed_word<PG>(a, pb + kw + 1u + (j >> 2));
+        const u32 d = __builtin_amdgcn_readfirstlane((dwd >> ((j & 3u) * 8u)) &
+                                                     (ECD_MAX_ROWS - 1u));
+        u32 acc[8][1];
+        row_product<K>(row, 0, kw, k, col, acc);
+        if (live)
+            store_chunk<1, true>(a.frag[d] + o, acc);
+    }
+}
+
 /* ------------------------------------------- ranged read: the edge stripes */
 
 /* Kernel arguments of ec_decode_clip: the k fragments, inv(mask) (k rows of kw

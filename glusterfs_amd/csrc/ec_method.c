@@ -2431,9 +2431,20 @@ typedef struct {
     size_t cap_masks, cap_pats; /* entries of masks[], bytes of pats[] */
 } ecm_setmemo_t;
 
+/* The same for ec_method_heal_mixed[_device]: the packed patterns of the last
+ * call's (mask, target mask) pairs (heal_mixed_patterns), one entry. */
+typedef struct {
+    uint64_t serial, hash;
+    uint32_t npairs;
+    uintptr_t *pairs; /* the masks, then the target masks */
+    uint8_t *pats;
+    size_t cap_pairs, cap_pats;
+} ecm_healmemo_t;
+
 typedef struct {
     ecm_setmemo_t e[ECM_SETMEMO];
     unsigned next;
+    ecm_healmemo_t heal;
 } ecm_setmemos_t;
 
 static pthread_key_t ecm_setmemo_key;
@@ -2450,6 +2461,8 @@ setmemo_free(void *v)
         free(s->e[i].masks);
         free(s->e[i].pats);
     }
+    free(s->heal.pairs);
+    free(s->heal.pats);
     free(s);
 }
 
@@ -2457,6 +2470,24 @@ static void
 setmemo_init(void)
 {
     ecm_setmemo_ok = pthread_key_create(&ecm_setmemo_key, setmemo_free) == 0;
+}
+
+/* the calling thread's memos, made at its first call; NULL: no memory */
+static ecm_setmemos_t *
+setmemos_get(void)
+{
+    ecm_setmemos_t *s;
+
+    pthread_once(&ecm_setmemo_once, setmemo_init);
+    s = ecm_setmemo_ok ? (ecm_setmemos_t *)pthread_getspecific(ecm_setmemo_key) : NULL;
+    if (!s && ecm_setmemo_ok) {
+        s = (ecm_setmemos_t *)calloc(1, sizeof(*s));
+        if (s && pthread_setspecific(ecm_setmemo_key, s) != 0) {
+            free(s);
+            s = NULL;
+        }
+    }
+    return s;
 }
 
 /* The packed patterns (k + k*k bytes each, in `masks` order) of a mask set;
@@ -2474,15 +2505,7 @@ pattern_set(ec_matrix_list_t *list, const uintptr_t *masks, uint32_t nmasks, int
 
     for (u = 0; u < nmasks; u++)
         h = (h ^ (uint64_t)masks[u]) * 1099511628211ull;
-    pthread_once(&ecm_setmemo_once, setmemo_init);
-    s = ecm_setmemo_ok ? (ecm_setmemos_t *)pthread_getspecific(ecm_setmemo_key) : NULL;
-    if (!s && ecm_setmemo_ok) {
-        s = (ecm_setmemos_t *)calloc(1, sizeof(*s));
-        if (s && pthread_setspecific(ecm_setmemo_key, s) != 0) {
-            free(s);
-            s = NULL;
-        }
-    }
+    s = setmemos_get();
     if (!s) {
         *rc = -ENOMEM;
         return NULL;
@@ -4426,6 +4449,280 @@ ecm_writev_rmw_device_impl(ec_matrix_list_t *list, int device, void *stream, uin
                                  CTX(list)->enc_pat);
 }
 
+/* ------------------------------------- fused heal with per-group patterns */
+
+/* Weak like ecd_writev_rmw_device: without the symbol
+ * ec_method_heal_mixed_device is -ENODEV. */
+extern __typeof__(ecd_heal_mixed) ecd_heal_mixed __attribute__((weak));
+
+#define ECM_HEAL_MIXED_TARGETS 15u /* the targets of one pattern: m is 0 ... 15 */
+
+/* an argument error of the mixed heal, with its reason for
+ * ec_method_last_error() */
+static int
+heal_mixed_inval(const char *why)
+{
+    char buf[160];
+
+    snprintf(buf, sizeof buf, "ec_method_heal_mixed: %s", why);
+    ecd_set_error(buf);
+    return -EINVAL;
+}
+
+/* What both entry points check first: the list, the fragment list, the two
+ * arrays that name the patterns (a, b: the group masks and targets of the
+ * host call, the pattern ids and masks of the device call) and a group of a
+ * power of two of at least 4 stripes, the kernel's tile.  *shift = its log2. */
+static int
+heal_mixed_args(ec_matrix_list_t *list, uint64_t group_stripes, const void *a, const void *b,
+                const void *const *frags, uint32_t *shift)
+{
+    if (!list || !CTX(list))
+        return heal_mixed_inval("no list");
+    if (!frags)
+        return heal_mixed_inval("no fragment list");
+    if (!a || !b)
+        return heal_mixed_inval("a mask, target or pattern array is NULL");
+    if (group_stripes < 4 || (group_stripes & (group_stripes - 1)))
+        return heal_mixed_inval("group_stripes is not a power of two of at least 4");
+    for (*shift = 2; (1ull << *shift) < group_stripes; (*shift)++)
+        ;
+    return 0;
+}
+
+/* One (mask, target mask) pair: k bricks of the volume as sources, targets
+ * inside the volume and apart from the sources, and a fragment for every
+ * brick named unless the target is empty -- then nothing of the group is
+ * touched and its fragments may be missing. */
+static int
+heal_mixed_pair(const ec_matrix_list_t *list, uintptr_t mask, uintptr_t target,
+                const void *const *frags)
+{
+    uint32_t b;
+
+    if (popcount_mask(mask) != list->columns || (mask >> list->rows) != 0)
+        return heal_mixed_inval("a mask is not k bricks of the volume");
+    if ((target >> list->rows) != 0)
+        return heal_mixed_inval("a target mask names a brick outside the volume");
+    if (target & mask)
+        return heal_mixed_inval("a target mask overlaps its mask");
+    if (popcount_mask(target) > ECM_HEAL_MIXED_TARGETS)
+        return heal_mixed_inval("a target mask has more than 15 bricks");
+    if (target == 0)
+        return 0;
+    for (b = 0; b < list->rows; b++)
+        if ((((mask | target) >> b) & 1) && !frags[b])
+            return heal_mixed_inval("a fragment of a mask or a target mask is NULL");
+    return 0;
+}
+
+/* The packed patterns of ecd_heal_mixed for np checked pairs, in their order:
+ * k + 1 + mmax + mmax * k bytes each -- the source bricks, m, the target
+ * bricks, and the m rows of the heal matrix, the arithmetic of heal_pattern()
+ * (the target rows of the encode matrix times inv(mask)).  *mmax = the largest
+ * m.  Kept per thread until the next call (a heal sweep repeats its pairs,
+ * and 64 masks of 16+4 cost 64 inversions); NULL with *rc set: no memory. */
+static const uint8_t *
+heal_mixed_patterns(ec_matrix_list_t *list, const uintptr_t *masks, const uintptr_t *targets,
+                    uint32_t np, uint32_t *mmax, int *rc)
+{
+    ecm_ctx_t *ctx = CTX(list);
+    const uint32_t k = list->columns;
+    ecm_setmemos_t *s = setmemos_get();
+    ecm_healmemo_t *e;
+    uint64_t h = 1469598103934665603ull; /* FNV-1a */
+    uint32_t rows[ECM_MAX_K], u, i, j, p, t, mm = 0, acc;
+    ecm_matrix_t *m;
+    size_t pb;
+
+    if (!s) {
+        *rc = -ENOMEM;
+        return NULL;
+    }
+    e = &s->heal;
+    for (u = 0; u < np; u++) {
+        h = (h ^ (uint64_t)masks[u]) * 1099511628211ull;
+        h = (h ^ (uint64_t)targets[u]) * 1099511628211ull;
+        t = popcount_mask(targets[u]);
+        mm = t > mm ? t : mm;
+    }
+    *mmax = mm;
+    if (e->serial == ctx->serial && e->npairs == np && e->hash == h &&
+        memcmp(e->pairs, masks, np * sizeof(*masks)) == 0 &&
+        memcmp(e->pairs + np, targets, np * sizeof(*targets)) == 0)
+        return e->pats;
+    e->serial = 0;
+    pb = (size_t)k + 1 + mm + (size_t)mm * k;
+    if (e->cap_pairs < 2u * np) {
+        uintptr_t *q = (uintptr_t *)realloc(e->pairs, 2u * np * sizeof(*q));
+
+        if (!q) {
+            *rc = -ENOMEM;
+            return NULL;
+        }
+        e->pairs = q;
+        e->cap_pairs = 2u * np;
+    }
+    if (e->cap_pats < np * pb) {
+        uint8_t *q = (uint8_t *)realloc(e->pats, np * pb);
+
+        if (!q) {
+            *rc = -ENOMEM;
+            return NULL;
+        }
+        e->pats = q;
+        e->cap_pats = np * pb;
+    }
+    memset(e->pats, 0, np * pb);
+    for (u = 0; u < np; u++) {
+        uint8_t *pat = e->pats + u * pb;
+
+        rows_from_mask(masks[u], rows);
+        for (p = 0; p < k; p++)
+            pat[p] = (uint8_t)(rows[p] - 1);
+        if (targets[u] == 0)
+            continue;
+        m = matrix_get(list, masks[u], rows);
+        if (!m) {
+            *rc = -ENOMEM;
+            return NULL;
+        }
+        for (i = 0, t = 0; i < list->rows; i++) {
+            if (!((targets[u] >> i) & 1))
+                continue;
+            pat[k + 1 + t] = (uint8_t)i;
+            for (p = 0; p < k; p++) {
+                acc = 0;
+                for (j = 0; j < k; j++)
+                    acc ^= ec_method_gf_mul(ctx->enc[i * k + j], m->inv[j * k + p]);
+                pat[k + 1 + mm + t * k + p] = (uint8_t)acc;
+            }
+            t++;
+        }
+        pat[k] = (uint8_t)t;
+        matrix_put(list, m);
+    }
+    memcpy(e->pairs, masks, np * sizeof(*masks));
+    memcpy(e->pairs + np, targets, np * sizeof(*targets));
+    e->npairs = np;
+    e->hash = h;
+    e->serial = ctx->serial;
+    return e->pats;
+}
+
+/* The byte-exact specification of the mixed heal, on the calling thread's CPU
+ * engine: the distinct pairs become patterns as in ecm_decode_mixed_impl, and
+ * every run of groups with one pattern is one combine from the run's source
+ * chunks to its target chunks. */
+static int32_t
+ecm_heal_mixed_impl(ec_matrix_list_t *list, uint64_t nstripes, uint64_t group_stripes,
+                    const uintptr_t *group_masks, const uintptr_t *group_targets,
+                    void *const *frags)
+{
+    uintptr_t um[ECD_MAX_PATTERNS], ut[ECD_MAX_PATTERNS];
+    const void *const *cf = (const void *const *)frags;
+    const uint8_t *pats, *pat;
+    ecd_combine_desc_t d;
+    uint8_t *gp;
+    uint64_t g, g1, ngroups, s0, s1;
+    uint32_t shift, nu = 0, u, k, mmax = 0, m, b, j;
+    size_t pb;
+    int rc;
+
+    rc = heal_mixed_args(list, group_stripes, group_masks, group_targets, cf, &shift);
+    if (rc)
+        return rc;
+    if (nstripes == 0)
+        return 0;
+    k = list->columns;
+    ngroups = (nstripes + group_stripes - 1) / group_stripes;
+    gp = (uint8_t *)malloc(ngroups);
+    if (!gp)
+        return -ENOMEM;
+    for (g = 0; g < ngroups && rc == 0; g++) {
+        for (u = 0; u < nu; u++)
+            if (um[u] == group_masks[g] && ut[u] == group_targets[g])
+                break;
+        if (u == nu) {
+            if (nu == ECD_MAX_PATTERNS) {
+                rc = -E2BIG;
+                break;
+            }
+            rc = heal_mixed_pair(list, group_masks[g], group_targets[g], cf);
+            if (rc)
+                break;
+            um[nu] = group_masks[g];
+            ut[nu++] = group_targets[g];
+        }
+        gp[g] = (uint8_t)u;
+    }
+    if (rc == 0 && !bufs_on(cf, list->rows, -1))
+        rc = heal_mixed_inval("a fragment is device memory");
+    pats = rc == 0 ? heal_mixed_patterns(list, um, ut, nu, &mmax, &rc) : NULL;
+    pb = (size_t)k + 1 + mmax + (size_t)mmax * k;
+    for (g = 0; g < ngroups && rc == 0; g = g1) {
+        for (g1 = g + 1; g1 < ngroups && gp[g1] == gp[g]; g1++)
+            ;
+        pat = pats + gp[g] * pb;
+        m = pat[k];
+        if (m == 0)
+            continue;
+        s0 = g << shift;
+        s1 = g1 << shift < nstripes ? g1 << shift : nstripes;
+        desc_init_frags(&d, k, m, s1 - s0);
+        for (b = 0; b < k; b++)
+            d.in_base[pat[b]] = (const uint8_t *)frags[pat[b]] + s0 * EC_METHOD_CHUNK_SIZE;
+        for (j = 0; j < m; j++)
+            d.out_base[j] = (uint8_t *)frags[pat[k + 1 + j]] + s0 * EC_METHOD_CHUNK_SIZE;
+        memcpy(d.pat, pat, k);
+        memcpy(d.pat + k, pat + k + 1 + mmax, (size_t)m * k);
+        rc = ecc_combine(CTX(list)->isa, &d);
+    }
+    free(gp);
+    return rc;
+}
+
+static int32_t
+ecm_heal_mixed_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                           uint64_t group_stripes, const uint8_t *group_pattern,
+                           uint32_t npatterns, const uintptr_t *masks,
+                           const uintptr_t *target_masks, void *const *frags)
+{
+    const void *const *cf = (const void *const *)frags;
+    void *fr[ECD_MAX_ROWS];
+    const uint8_t *pats;
+    uint32_t shift, u, mmax = 0;
+    int rc;
+
+    rc = heal_mixed_args(list, group_stripes, group_pattern, masks, cf, &shift);
+    if (rc)
+        return rc;
+    if (!target_masks)
+        return heal_mixed_inval("a mask, target or pattern array is NULL");
+    if (npatterns == 0)
+        return heal_mixed_inval("no patterns");
+    if (npatterns > ECD_MAX_PATTERNS)
+        return -E2BIG;
+    for (u = 0; u < npatterns; u++) {
+        rc = heal_mixed_pair(list, masks[u], target_masks[u], cf);
+        if (rc)
+            return rc;
+    }
+    if (nstripes == 0)
+        return 0;
+    if (!ecd_heal_mixed)
+        return -ENODEV;
+    if (!scrub_on_device(device, cf, list->rows, NULL, 0, NULL, 0, group_pattern, NULL))
+        return heal_mixed_inval("a buffer is not memory of the device");
+    pats = heal_mixed_patterns(list, masks, target_masks, npatterns, &mmax, &rc);
+    if (!pats)
+        return rc;
+    memset(fr, 0, sizeof fr);
+    memcpy(fr, frags, list->rows * sizeof(*fr));
+    return ecd_heal_mixed(device, stream, list->columns, nstripes, group_pattern, shift, npatterns,
+                          mmax, pats, fr);
+}
+
 /* ---------------------------------------------------- device-resident */
 
 static int32_t
@@ -4970,6 +5267,30 @@ ec_method_writev_rmw_device(ec_matrix_list_t *list, int device, void *stream, ui
     return ecm_ret("ec_method_writev_rmw_device", seq,
                    ecm_writev_rmw_device_impl(list, device, stream, head, size, user, mask,
                                               old_head, old_tail, out));
+}
+
+int32_t
+ec_method_heal_mixed(ec_matrix_list_t *list, uint64_t nstripes, uint64_t group_stripes,
+                     const uintptr_t *group_masks, const uintptr_t *group_targets,
+                     void *const *frags)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_mixed", seq,
+                   ecm_heal_mixed_impl(list, nstripes, group_stripes, group_masks, group_targets,
+                                       frags));
+}
+
+int32_t
+ec_method_heal_mixed_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nstripes,
+                            uint64_t group_stripes, const uint8_t *group_pattern,
+                            uint32_t npatterns, const uintptr_t *masks,
+                            const uintptr_t *target_masks, void *const *frags)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_mixed_device", seq,
+                   ecm_heal_mixed_device_impl(list, device, stream, nstripes, group_stripes,
+                                              group_pattern, npatterns, masks, target_masks,
+                                              frags));
 }
 
 int32_t

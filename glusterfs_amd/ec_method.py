@@ -66,6 +66,7 @@ EXPORTS = (
     "ec_method_scrub_report", "ec_method_scrub_report_device", "ec_method_scrub_report_work",
     "ec_method_readv_decode", "ec_method_readv_decode_device",
     "ec_method_writev_rmw", "ec_method_writev_rmw_device",
+    "ec_method_heal_mixed", "ec_method_heal_mixed_device",
 )
 
 
@@ -251,6 +252,9 @@ def _load():
         "ec_method_readv_decode_device": (i32, [P, ctypes.c_int, vp, u64, u64, up, vp, vp]),
         "ec_method_writev_rmw": (i32, [P, u64, vp, ctypes.c_int, up, vp, vp, vp]),
         "ec_method_writev_rmw_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, up, vp, vp,
+                                              vp]),
+        "ec_method_heal_mixed": (i32, [P, u64, u64, vp, vp, vp]),
+        "ec_method_heal_mixed_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, u32, vp, vp,
                                               vp]),
         "ec_method_config_fill": (None, [u32, u32, ctypes.POINTER(Config)]),
         "ec_method_config_pack": (i32, [ctypes.POINTER(Config), vp]),
@@ -562,6 +566,15 @@ class ECMatrixList:
                                                  group_stripes, gm, _ptr_array(frags),
                                                  addr(out)), "ec_method_decode_mixed")
 
+    def heal_mixed(self, nstripes, group_stripes, group_masks, group_targets, frags):
+        """ec_method_heal_mixed: `frags` is indexed by brick (None for a brick
+        no group with targets names) and is healed in place."""
+        gm = (ctypes.c_size_t * len(group_masks))(*group_masks)
+        gt = (ctypes.c_size_t * len(group_targets))(*group_targets)
+        return _check(lib.ec_method_heal_mixed(ctypes.byref(self._list), nstripes,
+                                               group_stripes, gm, gt, _ptr_array(frags)),
+                      "ec_method_heal_mixed")
+
     def writev_encode(self, head, user, old_head, old_tail, out):
         """ec_method_writev_encode: `user` is one buffer or a list of buffers
         (the writev iovec list); old_head / old_tail may be None."""
@@ -779,6 +792,16 @@ class ECMatrixList:
             ctypes.byref(self._list), device, stream, nstripes, group_stripes,
             addr(group_pattern), len(masks), m, _ptr_array(frags), addr(out)),
             "ec_method_decode_mixed_device")
+
+    def heal_mixed_device(self, device, stream, nstripes, group_stripes, group_pattern,
+                          masks, target_masks, frags):
+        """ec_method_heal_mixed_device: pattern u is (masks[u], target_masks[u])."""
+        m = (ctypes.c_size_t * len(masks))(*masks)
+        t = (ctypes.c_size_t * len(target_masks))(*target_masks)
+        return _check(lib.ec_method_heal_mixed_device(
+            ctypes.byref(self._list), device, stream, nstripes, group_stripes,
+            addr(group_pattern), len(masks), m, t, _ptr_array(frags)),
+            "ec_method_heal_mixed_device")
 
     def heal_device(self, device, stream, nstripes, mask, inp, target_mask, out):
         return _check(lib.ec_method_heal_device(ctypes.byref(self._list), device, stream,

@@ -167,6 +167,34 @@ int32_t ec_method_heal(ec_matrix_list_t *list, uint64_t nstripes, uintptr_t mask
                        const void *const *in, uintptr_t target_mask,
                        void *const *out);
 
+/* Fused heal with a pattern per stripe group: ec_method_heal for a batch in
+ * which the missing bricks -- and with them the bricks to read -- change from
+ * group to group, as ec_method_decode_mixed is for decodes.  frags[0..n) is
+ * indexed by brick (nstripes*512 bytes each).  Group g is the stripes
+ * [g*group_stripes, min((g+1)*group_stripes, nstripes)); group_stripes is a
+ * power of two of at least 4 (the device kernel's tile, which must have one
+ * pattern; the host call keeps the same rule).  For every stripe t of group g
+ * and every brick i in group_targets[g], chunk t of frags[i] becomes what
+ * ec_method_heal gives for that stripe from the k bricks in group_masks[g].
+ * Nothing else is written and the source chunks are only read, so the call
+ * works in place on the stored fragments: a target mask may not overlap its
+ * mask, and groups touch different stripes.  A group with an empty target mask
+ * is left alone and none of its chunks are read.  frags[i] may be NULL for a
+ * brick that no group names, or only groups with an empty target mask.
+ * Runs on the calling thread's CPU engine whatever the volume's engine is, and
+ * leaves ec_method_get_stats alone: it is the byte-exact specification of the
+ * device call below.
+ * -EINVAL (with the reason in ec_method_last_error()): list, frags, group_masks
+ * or group_targets NULL; group_stripes not a power of two or below 4; a mask
+ * that is not k bricks of the volume; a target mask with a bit at or above n,
+ * a bit of its mask or more than 15 bits; a NULL fragment for a brick of a
+ * mask or target mask whose target mask is not empty; a fragment in device
+ * memory.  -E2BIG: more than 256 distinct (mask, target mask) pairs.
+ * nstripes == 0 returns 0 after the first checks and touches nothing. */
+int32_t ec_method_heal_mixed(ec_matrix_list_t *list, uint64_t nstripes, uint64_t group_stripes,
+                             const uintptr_t *group_masks, const uintptr_t *group_targets,
+                             void *const *frags);
+
 /* Consistency check: do the fragments of the bricks in check_mask agree with
  * the k fragments in mask?  in[p] = fragment of the p-th set bit of mask,
  * check[j] = stored fragment of the j-th set bit of check_mask (nstripes*512
@@ -938,6 +966,25 @@ int32_t ec_method_writev_rmw_device(ec_matrix_list_t *list, int device, void *st
                                     uint64_t head, uint64_t size, const void *user,
                                     uintptr_t mask, const void *const *old_head,
                                     const void *const *old_tail, void *const *out);
+/* ec_method_heal_mixed on device buffers.  Group g uses pattern
+ * group_pattern[g], a device array of a byte per group as for
+ * ec_method_decode_mixed_device (ids >= npatterns are clamped to the last
+ * pattern); pattern u is the pair (masks[u], target_masks[u]), host arrays
+ * read during the call, npatterns <= 256 (-E2BIG beyond, -EINVAL for 0).
+ * Every pattern is checked as the host call checks a group's pair, whether a
+ * group uses it or not; every non-NULL fragment and group_pattern must be
+ * memory of `device` (-EINVAL), and -ENODEV where the device layer lacks the
+ * call.  One launch of one kernel, asynchronous on `stream`, with no host
+ * synchronisation, no pre-zeroing and no atomics; patterns with different
+ * numbers of targets may share a call.  Pattern sets that fit the 2 KiB
+ * kernel-argument segment travel there; larger ones (64 masks of 16+4, up to
+ * all 256 patterns of any geometry) go to a cached device table, uploaded on
+ * `stream` the first time a set is seen. */
+int32_t ec_method_heal_mixed_device(ec_matrix_list_t *list, int device, void *stream,
+                                    uint64_t nstripes, uint64_t group_stripes,
+                                    const uint8_t *group_pattern, uint32_t npatterns,
+                                    const uintptr_t *masks, const uintptr_t *target_masks,
+                                    void *const *frags);
 int32_t ec_method_sync_device(int device, void *stream);
 
 /* ------------------------------------------------------------------------
