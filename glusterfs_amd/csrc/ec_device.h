@@ -282,6 +282,26 @@ int ecd_heal_mixed(int device, void *stream, uint32_t k, uint64_t nstripes,
                    const uint8_t *group_pattern, uint32_t group_shift, uint32_t npatterns,
                    uint32_t mmax, const uint8_t *pats, void *const *frags);
 
+/* ec_method_extent_t as the device layer reads it: 32 fragment addresses
+ * indexed by brick, then first, nstripes, pattern and a zero word. */
+#define ECD_EXTENT_BYTES 272u
+#define ECD_EXTENT_FIRST 256u
+
+/* Fused heal over a table of extents, on device memory (asynchronous on
+ * `stream`; ec_method_heal_extents_device): ext_dev is nextents records of
+ * ECD_EXTENT_BYTES in memory of `device`, 8-byte aligned, whose `first` fields
+ * are the running sum of ceil(nstripes / 4) and add up to ntiles.  pats
+ * (host memory, read during the call): npatterns packed patterns as for
+ * ecd_heal_mixed.  For every extent whose pattern has m > 0, every stripe t of
+ * it and every j < m, chunk t of its frag[dst[j]] becomes the sum over p of
+ * coef[j][p] * chunk t of its frag[src[p]]; nothing else is written.  in_bytes
+ * (the bytes the call reads, 0: unknown) and aligned (every fragment address
+ * is a multiple of 16) choose the staging policy, as ecd_heal_mixed does from
+ * its own arguments.  One launch of ec_heal_extents_n. */
+int ecd_heal_extents(int device, void *stream, uint32_t k, uint64_t nextents, uint64_t ntiles,
+                     const void *ext_dev, uint32_t npatterns, uint32_t mmax,
+                     const uint8_t *pats, uint64_t in_bytes, int aligned);
+
 /* Decode / reconstruct: frags[0..nfrags) are fragment buffers of
  * nstripes*512 bytes (NULL for fragments no pattern reads).  Output: when
  * outs is NULL, out = nstripes*rows*512 bytes, stripe-major (decoded data);

@@ -1973,6 +1973,16 @@ int ecd_heal_mixed(int device, void *stream, uint32_t k, uint64_t nstripes,
     });
 }
 
+int ecd_heal_extents(int device, void *stream, uint32_t k, uint64_t nextents, uint64_t ntiles,
+                     const void *ext_dev, uint32_t npatterns, uint32_t mmax,
+                     const uint8_t *pats, uint64_t in_bytes, int aligned)
+{
+    return on_device(device, stream, [&](hipStream_t s) {
+        return ecdk_heal_extents(s, k, nextents, ntiles, ext_dev, npatterns, mmax, pats, in_bytes,
+                                 aligned);
+    });
+}
+
 int ecd_decode_host(int ndev, uint32_t k, uint32_t rows, uint64_t nstripes, uint32_t nfrags,
                     const void *const *frags, void *out, void *const *outs, uint32_t npatterns,
                     const uint8_t *pats, const uint8_t *group_pattern, uint32_t group_shift)

@@ -79,6 +79,12 @@ int ecdk_rmw_edge(hipStream_t s, uint32_t k, uint32_t n, const uint8_t *inv, con
 int ecdk_heal_mixed(hipStream_t s, uint32_t k, uint64_t nstripes, const uint8_t *group_pattern,
                     uint32_t group_shift, uint32_t npatterns, uint32_t mmax, const uint8_t *pats,
                     void *const *frags);
+/* The fused heal over a table of extents of ecd_heal_extents
+ * (ec_heal_extents_n): tile b of the ntiles belongs to the last record of
+ * ext_dev whose `first` is at most b.  pats as for ecdk_heal_mixed. */
+int ecdk_heal_extents(hipStream_t s, uint32_t k, uint64_t nextents, uint64_t ntiles,
+                      const void *ext_dev, uint32_t npatterns, uint32_t mmax,
+                      const uint8_t *pats, uint64_t in_bytes, int aligned);
 /* 1 when ecdk_encode_vander(k, n) reads its input at any byte alignment (the
  * tile encoders), 0 when it wants 16-byte alignment (the register encoder) */
 int ecdk_encode_any_alignment(uint32_t k, uint32_t n);

@@ -1362,6 +1362,110 @@ int ecdk_heal_mixed(hipStream_t s, uint32_t k, uint64_t nstripes, const uint8_t 
     return rc;
 }
 
+/* ---------------------------------------- fused heal over a table of extents */
+
+namespace {
+
+/* the instantiation of ec_heal_extents_n, as launch_heal_mixed */
+template <bool PG, int LA>
+int launch_heal_extents(hipStream_t s, const HealExtentsArgs &a, u32 g)
+{
+    const size_t lds = scrub_tile_lds(a.k, 0);
+    if (a.k <= 4)
+        hipLaunchKernelGGL((ec_heal_extents_n<4, 4, PG, LA>), dim3(g), dim3(4 * 64), lds, s, a);
+    else if (a.k <= 8)
+        hipLaunchKernelGGL((ec_heal_extents_n<8, 8, PG, LA>), dim3(g), dim3(8 * 64), lds, s, a);
+    else
+        hipLaunchKernelGGL((ec_heal_extents_n<16, 8, PG, LA>), dim3(g), dim3(8 * 64), lds, s, a);
+    return launch_ok("launch_heal_extents");
+}
+
+} // namespace
+
+/* pats: as for ecdk_heal_mixed.  One launch of ntiles blocks; the patterns
+ * travel in the kernel arguments when they fit and in a table of the pattern
+ * cache when not.  The fragment addresses stay in the caller's table. */
+int ecdk_heal_extents(hipStream_t s, uint32_t k, uint64_t nextents, uint64_t ntiles,
+                      const void *ext_dev, uint32_t npatterns, uint32_t mmax,
+                      const uint8_t *pats, uint64_t in_bytes, int aligned)
+{
+    static_assert(sizeof(HealExtentsArgs) <= 2048, "the arguments keep to 2 KiB");
+    static_assert(offsetof(HealExtentsArgs, pat) == 40, "the header the tests count");
+    HealExtentsArgs a;
+    if (k == 0 || k > ECD_MAX_K || !ext_dev || ((uintptr_t)ext_dev & 7u) || npatterns == 0 ||
+        npatterns > ECD_MAX_PATTERNS || mmax >= 16 || !pats || nextents > ntiles ||
+        ntiles > 0x7fffffffull)
+        return -EINVAL;
+    if (nextents == 0 || mmax == 0)
+        return 0;               /* no extent, or no pattern with a target */
+    memset(&a, 0, sizeof(a));
+    a.ext = static_cast<const uint8_t *>(ext_dev);
+    a.nextents = (u32)nextents;
+    a.k = k;
+    a.kw = (k + 3) / 4;
+    a.npatterns = npatterns;
+    a.dw = (mmax + 3) / 4;
+    a.pwords = a.kw + 1 + a.dw + mmax * a.kw;
+    const size_t pbytes = (size_t)k + 1 + mmax + (size_t)mmax * k;
+    const size_t nw = (size_t)a.pwords * npatterns;
+    const bool pg = nw > (size_t)kHealExtentsPatWords;
+    std::vector<u32> table(pg ? nw : 0, 0u);
+    u32 *words = pg ? table.data() : a.pat;
+    for (u32 q = 0; q < npatterns; ++q) {
+        const uint8_t *src = pats + q * pbytes;
+        uint8_t *dst = reinterpret_cast<uint8_t *>(words + (size_t)q * a.pwords);
+        const u32 m = src[k];
+        if (m > mmax)
+            return -EINVAL;
+        for (u32 p = 0; p < k; ++p)
+            if (src[p] >= ECD_MAX_ROWS)
+                return -EINVAL;
+        memcpy(dst, src, k);
+        dst[4 * a.kw] = (uint8_t)m;
+        for (u32 j = 0; j < m; ++j) {
+            if (src[k + 1 + j] >= ECD_MAX_ROWS)
+                return -EINVAL;
+            dst[4 * (a.kw + 1) + j] = src[k + 1 + j];
+            memcpy(dst + 4 * (a.kw + 1 + a.dw + (size_t)j * a.kw), src + k + 1 + mmax + j * k, k);
+        }
+    }
+    u32 *tab = nullptr;
+    PatTableCache::Ref ref;
+    int rc = 0;
+    if (pg) {
+        rc = pat_tables().acquire(s, table, ref);
+        if (rc == 0) {
+            a.patg = ref.ptr;
+        } else if (rc == -EBUSY) {
+            /* every cache entry in use: a table of this call's own */
+            if (const hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&tab), nw * 4, s)) {
+                (void)hip_ok(e, "hipMallocAsync(per-call pattern table)");
+                return -ENOMEM;
+            }
+            a.patg = tab;
+            rc = enqueue_upload(s, table, tab);
+        }
+    }
+    if (rc == 0) {
+        /* the staging policy of ecdk_heal_mixed; a caller that cannot tell
+         * where its fragments lie gets the default policy */
+        const bool nt = aligned && nt_staging(in_bytes);
+        if (pg)
+            rc = nt ? launch_heal_extents<true, kLdsDmaNT>(s, a, (u32)ntiles)
+                    : launch_heal_extents<true, kLdsDmaDefault>(s, a, (u32)ntiles);
+        else
+            rc = nt ? launch_heal_extents<false, kLdsDmaNT>(s, a, (u32)ntiles)
+                    : launch_heal_extents<false, kLdsDmaDefault>(s, a, (u32)ntiles);
+    }
+    if (ref.slot >= 0)
+        (void)pat_tables().release(ref, s);   /* a failure drained s: the call stands */
+    if (tab) {
+        const int frc = hip_ok(hipFreeAsync(tab, s), "hipFreeAsync(per-call pattern table)");
+        rc = rc ? rc : frc;
+    }
+    return rc;
+}
+
 /* ------------------------------------------- ranged read: the edge stripes */
 
 /* in: the k fragments (device memory, any byte alignment); inv: k x k bytes,

@@ -2458,6 +2458,128 @@ __global__ __launch_bounds__(NW * 64) void ec_heal_mixed_n(const HealMixedArgs a
     }
 }
 
+/* ---------------------------------------- fused heal over a table of extents */
+
+/* Kernel arguments of ec_heal_extents_n.  ext: the nextents records of
+ * ec_method_extent_t in device memory (ECD_EXTENT_BYTES each: 32 fragment
+ * addresses indexed by brick, then first, nstripes, pattern and a zero word at
+ * ECD_EXTENT_FIRST).  The patterns are packed as for ec_heal_mixed_n, in pat[]
+ * (PG = false) or in the device table patg (PG = true).  Without the 32 brick
+ * pointers the header is 40 bytes, so pat[] has 502 words where HealMixedArgs
+ * has 436; 2,048 bytes in all. */
+constexpr int kHealExtentsPatWords = 502;
+
+struct HealExtentsArgs {
+    const uint8_t *ext;
+    const u32 *patg;
+    u32 nextents, k, kw, npatterns, pwords, dw;
+    u32 pat[kHealExtentsPatWords];
+};
+
+template <bool PG>
+__device__ __forceinline__ u32 heal_extents_word(const HealExtentsArgs &a, u32 idx)
+{
+    if constexpr (PG)
+        return scalar_load_u32(a.patg + idx);
+    else
+        return a.pat[idx];
+}
+
+/* a wave-uniform 64-bit word of read-only global memory, as scalar_load_u32 */
+__device__ __forceinline__ uint64_t scalar_load_u64(const void *p)
+{
+    const uintptr_t a = (uintptr_t)p;
+    return *reinterpret_cast<const __attribute__((address_space(4))) uint64_t *>(a);
+}
+
+/* The extent that owns `tile`: the last record of ext[0 .. n) whose `first` is
+ * at most `tile`, by a binary search of scalar loads (one 64-byte line of the
+ * scalar cache per step, the upper steps shared by every block; a 64-way
+ * search by a wave would touch 64 lines per step, a record being 272 bytes).
+ * [lo, lo + n) shrinks at every step whatever the words hold, so the loop ends
+ * after at most 31 steps, and only records below n are read. */
+__device__ __forceinline__ u32 extent_of_tile(const uint8_t *ext, u32 n, u32 tile)
+{
+    u32 lo = 0;
+    while (n > 1) {
+        const u32 h = n >> 1;
+        const u32 f = scalar_load_u32(ext + (uint64_t)(lo + h) * ECD_EXTENT_BYTES +
+                                      ECD_EXTENT_FIRST);
+        if (f <= tile) {
+            lo += h;
+            n -= h;
+        } else {
+            n = h;
+        }
+    }
+    return __builtin_amdgcn_readfirstlane(lo);
+}
+
+/* ec_method_heal_extents_device: ec_heal_mixed_n with the fragments of the
+ * tile's extent in place of one fragment list per call.  Block b finds the
+ * extent that owns tile b (extent_of_tile), reads first, nstripes and pattern
+ * from its record by one scalar load, and heals stripes (b - first) * kScrubT
+ * and on of that extent: the k source chunks come from the record's frag[]
+ * words of the pattern's src[] bricks, loaded as scalars when stage_tile asks
+ * for them, and row j goes to the record's frag[dst[j]].  A pattern id past
+ * the table clamps to the last pattern; a pattern without targets returns
+ * before any fragment word is read; stripes at or past the extent's nstripes
+ * are neither staged nor stored, and a null target is not stored to.  Extents
+ * own their target chunks, so no block depends on another. */
+template <int K, int NW, bool PG, int LA = kLdsDmaDefault>
+__global__ __launch_bounds__(NW * 64) void ec_heal_extents_n(const HealExtentsArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const u32 tid = threadIdx.x;
+    const u32 wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const u32 lane = tid & 63u;
+    const u32 k = a.k, kw = a.kw;
+    const uint8_t *rec = a.ext + (uint64_t)extent_of_tile(a.ext, a.nextents, blockIdx.x) *
+                                     ECD_EXTENT_BYTES;
+    const v4u hd = *reinterpret_cast<const __attribute__((address_space(4))) v4u *>(
+        (uintptr_t)(rec + ECD_EXTENT_FIRST));
+    const uint64_t t0 = (uint64_t)(blockIdx.x - hd.x) * kScrubT;
+    const uint64_t ns = hd.y;
+    const u32 pb = (hd.z < a.npatterns ? hd.z : a.npatterns - 1u) * a.pwords;
+    const u32 m = __builtin_amdgcn_readfirstlane(heal_extents_word<PG>(a, pb + kw));
+    if (m == 0)
+        return;
+    const u32 s0 = heal_extents_word<PG>(a, pb);
+    const u32 s1 = K > 4 ? heal_extents_word<PG>(a, pb + 1) : 0u;
+    const u32 s2 = K > 8 ? heal_extents_word<PG>(a, pb + 2) : 0u;
+    const u32 s3 = K > 8 ? heal_extents_word<PG>(a, pb + 3) : 0u;
+    stage_tile<kScrubT, NW, LA>(lds, [&](u32 p, uint64_t st) -> const uint8_t * {
+        const u32 q = p >> 2;
+        const u32 w = (s0 & (0u - (u32)(q == 0))) | (s1 & (0u - (u32)(q == 1))) |
+                      (s2 & (0u - (u32)(q == 2))) | (s3 & (0u - (u32)(q == 3)));
+        const u32 b = __builtin_amdgcn_readfirstlane((w >> ((p & 3u) * 8u)) & (ECD_MAX_ROWS - 1u));
+        const uint8_t *f = reinterpret_cast<const uint8_t *>(scalar_load_u64(rec + b * 8u));
+        return f ? f + st * ECD_CHUNK : nullptr;
+    }, k, t0, ns, wave, lane);
+    __syncthreads();
+    const u32 cs = lane >> 4, cc = lane & 15u;
+    const uint8_t *col = lds + cs * 64u + cc * 4u;
+    const bool live = t0 + cs < ns;
+    const uint64_t o = (t0 + cs) * (uint64_t)ECD_CHUNK + cc * 4u;
+    const u32 rows = pb + kw + 1u + a.dw;
+    for (u32 j = wave; j < m; j += NW) {
+        const u32 rj = rows + j * kw;
+        u32 row[4];
+        row[0] = heal_extents_word<PG>(a, rj);
+        row[1] = K > 4 ? heal_extents_word<PG>(a, rj + 1) : 0u;
+        row[2] = K > 8 ? heal_extents_word<PG>(a, rj + 2) : 0u;
+        row[3] = K > 8 && kw > 3 ? heal_extents_word<PG>(a, rj + 3) : 0u;
+        const u32 dwd = heal_extents_word<PG>(a, pb + kw + 1u + (j >> 2));
+        const u32 d = __builtin_amdgcn_readfirstlane((dwd >> ((j & 3u) * 8u)) &
+                                                     (ECD_MAX_ROWS - 1u));
+        uint8_t *dst = reinterpret_cast<uint8_t *>(scalar_load_u64(rec + d * 8u));
+        u32 acc[8][1];
+        row_product<K>(row, 0, kw, k, col, acc);
+        if (live && dst)
+            store_chunk<1, true>(dst + o, acc);
+    }
+}
+
 /* ------------------------------------------- ranged read: the edge stripes */
 
 /* Kernel arguments of ec_decode_clip: the k fragments, inv(mask) (k rows of kw

@@ -4723,6 +4723,235 @@ ecm_heal_mixed_device_impl(ec_matrix_list_t *list, int device, void *stream, uin
                           mmax, pats, fr);
 }
 
+/* ---------------------------------------- fused heal over a table of extents */
+
+/* Weak like ecd_heal_mixed: without the symbol ec_method_heal_extents_device
+ * is -ENODEV. */
+extern __typeof__(ecd_heal_extents) ecd_heal_extents __attribute__((weak));
+
+_Static_assert(sizeof(ec_method_extent_t) == ECD_EXTENT_BYTES, "the record the kernel reads");
+_Static_assert(offsetof(ec_method_extent_t, first) == ECD_EXTENT_FIRST &&
+                   offsetof(ec_method_extent_t, nstripes) == ECD_EXTENT_FIRST + 4 &&
+                   offsetof(ec_method_extent_t, pattern) == ECD_EXTENT_FIRST + 8,
+               "the record the kernel reads");
+_Static_assert(EC_MI355X_EXTENT_TILE == 4, "the 4-stripe scrub tile");
+
+#define ECM_EXTENT_TILES 0x7fffffffull /* the tiles of one call: a launch's blocks */
+
+static int
+heal_extents_inval(const char *why)
+{
+    char buf[160];
+
+    snprintf(buf, sizeof buf, "ec_method_heal_extents: %s", why);
+    ecd_set_error(buf);
+    return -EINVAL;
+}
+
+static uint64_t
+extent_tiles(const ec_method_extent_t *r)
+{
+    return ((uint64_t)r->nstripes + EC_MI355X_EXTENT_TILE - 1) / EC_MI355X_EXTENT_TILE;
+}
+
+/* What both entry points check first, and every pattern by the rules of
+ * heal_mixed_pair (a fragment list without holes: where an extent's fragments
+ * lie is the table's matter), its reason under this call's name. */
+static int
+heal_extents_args(ec_matrix_list_t *list, const void *ext, uint32_t npatterns,
+                  const uintptr_t *masks, const uintptr_t *targets)
+{
+    static const char here = 0;
+    const void *all[ECD_MAX_ROWS];
+    char why[128];
+    const char *text;
+    uint32_t u;
+
+    if (!list || !CTX(list))
+        return heal_extents_inval("no list");
+    if (!ext)
+        return heal_extents_inval("no extent table");
+    if (!masks || !targets)
+        return heal_extents_inval("a mask or target array is NULL");
+    if (npatterns == 0)
+        return heal_extents_inval("no patterns");
+    if (npatterns > ECD_MAX_PATTERNS)
+        return -E2BIG;
+    for (u = 0; u < ECD_MAX_ROWS; u++)
+        all[u] = &here;
+    for (u = 0; u < npatterns; u++)
+        if (heal_mixed_pair(list, masks[u], targets[u], all) != 0) {
+            text = strstr(ecd_last_error(), ": ");
+            snprintf(why, sizeof why, "%s", text ? text + 2 : "a bad pattern");
+            return heal_extents_inval(why);
+        }
+    return 0;
+}
+
+/* A host copy of the table against the rules of the header: the records, the
+ * running sum (*tiles = the total), and for every extent whose pattern has
+ * targets the fragments of its mask and target mask, present and on `dev`
+ * (-1: host memory).  *stripes and *align gather what the staging policy
+ * asks: the stripes that are read and the OR of their fragments' addresses. */
+static int
+heal_extents_table(const ec_matrix_list_t *list, uint64_t nextents, const ec_method_extent_t *ext,
+                   uint32_t npatterns, const uintptr_t *masks, const uintptr_t *targets, int dev,
+                   uint64_t *tiles, uint64_t *stripes, uintptr_t *align)
+{
+    uint64_t e, sum = 0;
+    uintptr_t need;
+    uint32_t b;
+
+    *stripes = 0;
+    *align = 0;
+    for (e = 0; e < nextents; e++) {
+        const ec_method_extent_t *r = &ext[e];
+
+        if (r->nstripes == 0)
+            return heal_extents_inval("an extent has no stripes");
+        if (r->zero != 0)
+            return heal_extents_inval("the zero field of an extent is not 0");
+        if (r->pattern >= npatterns)
+            return heal_extents_inval("the pattern of an extent is not below npatterns");
+        if (r->first != sum)
+            return heal_extents_inval("the first of an extent is not the tiles before it");
+        sum += extent_tiles(r);
+        if (sum > ECM_EXTENT_TILES)
+            return heal_extents_inval("more than 2^31 - 1 tiles");
+        if (targets[r->pattern] == 0)
+            continue;
+        need = masks[r->pattern] | targets[r->pattern];
+        for (b = 0; b < list->rows; b++) {
+            if (!((need >> b) & 1))
+                continue;
+            if (r->frag[b] == 0)
+                return heal_extents_inval("a fragment of a mask or a target mask is 0");
+            if (ecd_ptr_device((const void *)(uintptr_t)r->frag[b]) != dev)
+                return heal_extents_inval(dev < 0 ? "a fragment is device memory"
+                                                  : "a fragment is not memory of the device");
+            *align |= (uintptr_t)r->frag[b];
+        }
+        *stripes += r->nstripes;
+    }
+    *tiles = sum;
+    return 0;
+}
+
+static int64_t
+ecm_extents_layout_impl(uint64_t nextents, ec_method_extent_t *ext)
+{
+    uint64_t e, sum = 0;
+
+    if (nextents == 0)
+        return 0;
+    if (!ext)
+        return heal_extents_inval("no extent table");
+    for (e = 0; e < nextents; e++) {
+        if (ext[e].nstripes == 0)
+            return heal_extents_inval("an extent has no stripes");
+        sum += extent_tiles(&ext[e]);
+        if (sum > ECM_EXTENT_TILES)
+            return heal_extents_inval("more than 2^31 - 1 tiles");
+    }
+    for (e = 0, sum = 0; e < nextents; e++) {
+        ext[e].first = (uint32_t)sum;
+        sum += extent_tiles(&ext[e]);
+    }
+    return (int64_t)sum;
+}
+
+/* The byte-exact specification of the extent heal, on the calling thread's
+ * CPU engine: every extent whose pattern has targets is one combine from its
+ * source fragments to its target fragments, as ecm_heal_mixed_impl runs a
+ * pattern run. */
+static int32_t
+ecm_heal_extents_impl(ec_matrix_list_t *list, uint64_t nextents, const ec_method_extent_t *ext,
+                      uint32_t npatterns, const uintptr_t *masks, const uintptr_t *targets)
+{
+    const uint8_t *pats, *pat;
+    ecd_combine_desc_t d;
+    uint64_t e, tiles, stripes;
+    uintptr_t align;
+    uint32_t k, mmax = 0, m, b, j;
+    size_t pb;
+    int rc;
+
+    rc = heal_extents_args(list, ext, npatterns, masks, targets);
+    if (rc)
+        return rc;
+    if (nextents == 0)
+        return 0;
+    if (ecd_ptr_device(ext) >= 0)
+        return heal_extents_inval("the extent table is device memory");
+    rc = heal_extents_table(list, nextents, ext, npatterns, masks, targets, -1, &tiles, &stripes,
+                            &align);
+    if (rc)
+        return rc;
+    k = list->columns;
+    pats = heal_mixed_patterns(list, masks, targets, npatterns, &mmax, &rc);
+    if (!pats)
+        return rc;
+    pb = (size_t)k + 1 + mmax + (size_t)mmax * k;
+    for (e = 0; e < nextents && rc == 0; e++) {
+        pat = pats + ext[e].pattern * pb;
+        m = pat[k];
+        if (m == 0)
+            continue;
+        desc_init_frags(&d, k, m, ext[e].nstripes);
+        for (b = 0; b < k; b++)
+            d.in_base[pat[b]] = (const uint8_t *)(uintptr_t)ext[e].frag[pat[b]];
+        for (j = 0; j < m; j++)
+            d.out_base[j] = (uint8_t *)(uintptr_t)ext[e].frag[pat[k + 1 + j]];
+        memcpy(d.pat, pat, k);
+        memcpy(d.pat + k, pat + k + 1 + mmax, (size_t)m * k);
+        rc = ecc_combine(CTX(list)->isa, &d);
+    }
+    return rc;
+}
+
+static int32_t
+ecm_heal_extents_device_impl(ec_matrix_list_t *list, int device, void *stream, uint64_t nextents,
+                             uint64_t ntiles, const ec_method_extent_t *ext_dev,
+                             const ec_method_extent_t *ext_host, uint32_t npatterns,
+                             const uintptr_t *masks, const uintptr_t *targets)
+{
+    const uint8_t *pats;
+    uint64_t tiles = 0, stripes = 0;
+    uintptr_t align = 1; /* unknown fragments: not known to be aligned */
+    uint32_t mmax = 0;
+    int rc;
+
+    rc = heal_extents_args(list, ext_dev, npatterns, masks, targets);
+    if (rc)
+        return rc;
+    if (nextents == 0)
+        return 0;
+    if (nextents > ntiles || ntiles > ECM_EXTENT_TILES)
+        return heal_extents_inval("ntiles is not the total of the table");
+    if (!ecd_heal_extents)
+        return -ENODEV;
+    if (device < 0 || ecd_ptr_device(ext_dev) != device)
+        return heal_extents_inval("the extent table is not memory of the device");
+    if ((uintptr_t)ext_dev & 7u)
+        return heal_extents_inval("the extent table is not 8-byte aligned");
+    if (ext_host) {
+        if (ecd_ptr_device(ext_host) >= 0)
+            return heal_extents_inval("the host copy of the extent table is device memory");
+        rc = heal_extents_table(list, nextents, ext_host, npatterns, masks, targets, device,
+                                &tiles, &stripes, &align);
+        if (rc)
+            return rc;
+        if (tiles != ntiles)
+            return heal_extents_inval("ntiles is not the total of the table");
+    }
+    pats = heal_mixed_patterns(list, masks, targets, npatterns, &mmax, &rc);
+    if (!pats)
+        return rc;
+    return ecd_heal_extents(device, stream, list->columns, nextents, ntiles, ext_dev, npatterns,
+                            mmax, pats, stripes * list->columns * EC_METHOD_CHUNK_SIZE,
+                            (align & 15u) == 0);
+}
+
 /* ---------------------------------------------------- device-resident */
 
 static int32_t
@@ -5291,6 +5520,33 @@ ec_method_heal_mixed_device(ec_matrix_list_t *list, int device, void *stream, ui
                    ecm_heal_mixed_device_impl(list, device, stream, nstripes, group_stripes,
                                               group_pattern, npatterns, masks, target_masks,
                                               frags));
+}
+
+int64_t
+ec_method_extents_layout(uint64_t nextents, ec_method_extent_t *ext)
+{
+    return ecm_extents_layout_impl(nextents, ext);
+}
+
+int32_t
+ec_method_heal_extents(ec_matrix_list_t *list, uint64_t nextents, const ec_method_extent_t *ext,
+                       uint32_t npatterns, const uintptr_t *masks, const uintptr_t *target_masks)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_extents", seq,
+                   ecm_heal_extents_impl(list, nextents, ext, npatterns, masks, target_masks));
+}
+
+int32_t
+ec_method_heal_extents_device(ec_matrix_list_t *list, int device, void *stream, uint64_t nextents,
+                              uint64_t ntiles, const ec_method_extent_t *ext_dev,
+                              const ec_method_extent_t *ext_host, uint32_t npatterns,
+                              const uintptr_t *masks, const uintptr_t *target_masks)
+{
+    const uint64_t seq = ecd_error_seq();
+    return ecm_ret("ec_method_heal_extents_device", seq,
+                   ecm_heal_extents_device_impl(list, device, stream, nextents, ntiles, ext_dev,
+                                                ext_host, npatterns, masks, target_masks));
 }
 
 int32_t

@@ -67,6 +67,7 @@ EXPORTS = (
     "ec_method_readv_decode", "ec_method_readv_decode_device",
     "ec_method_writev_rmw", "ec_method_writev_rmw_device",
     "ec_method_heal_mixed", "ec_method_heal_mixed_device",
+    "ec_method_extents_layout", "ec_method_heal_extents", "ec_method_heal_extents_device",
 )
 
 
@@ -147,6 +148,17 @@ class Config(ctypes.Structure):
     def astuple(self):
         return (self.version, self.algorithm, self.gf_word_size, self.bricks,
                 self.redundancy, self.chunk_size)
+
+
+class Extent(ctypes.Structure):
+    """ec_method_extent_t: one window of ec_method_heal_extents[_device]."""
+    _fields_ = [
+        ("frag", ctypes.c_uint64 * 32),
+        ("first", ctypes.c_uint32),
+        ("nstripes", ctypes.c_uint32),
+        ("pattern", ctypes.c_uint32),
+        ("zero", ctypes.c_uint32),
+    ]
 
 
 def _load():
@@ -256,6 +268,10 @@ def _load():
         "ec_method_heal_mixed": (i32, [P, u64, u64, vp, vp, vp]),
         "ec_method_heal_mixed_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, u32, vp, vp,
                                               vp]),
+        "ec_method_extents_layout": (ctypes.c_int64, [u64, vp]),
+        "ec_method_heal_extents": (i32, [P, u64, vp, u32, vp, vp]),
+        "ec_method_heal_extents_device": (i32, [P, ctypes.c_int, vp, u64, u64, vp, vp, u32, vp,
+                                                vp]),
         "ec_method_config_fill": (None, [u32, u32, ctypes.POINTER(Config)]),
         "ec_method_config_pack": (i32, [ctypes.POINTER(Config), vp]),
         "ec_method_config_unpack": (i32, [vp, ctypes.c_size_t, ctypes.POINTER(Config)]),
@@ -575,6 +591,15 @@ class ECMatrixList:
                                                group_stripes, gm, gt, _ptr_array(frags)),
                       "ec_method_heal_mixed")
 
+    def heal_extents(self, table, masks, target_masks, nextents=None):
+        """ec_method_heal_extents: `table` is an array of Extent in host memory
+        (extent_table) whose fragments are host addresses, healed in place."""
+        m = (ctypes.c_size_t * len(masks))(*masks)
+        t = (ctypes.c_size_t * len(target_masks))(*target_masks)
+        n = len(table) if nextents is None else nextents
+        return _check(lib.ec_method_heal_extents(ctypes.byref(self._list), n, addr(table),
+                                                 len(masks), m, t), "ec_method_heal_extents")
+
     def writev_encode(self, head, user, old_head, old_tail, out):
         """ec_method_writev_encode: `user` is one buffer or a list of buffers
         (the writev iovec list); old_head / old_tail may be None."""
@@ -803,6 +828,16 @@ class ECMatrixList:
             addr(group_pattern), len(masks), m, t, _ptr_array(frags)),
             "ec_method_heal_mixed_device")
 
+    def heal_extents_device(self, device, stream, nextents, ntiles, ext_dev, ext_host, masks,
+                            target_masks):
+        """ec_method_heal_extents_device: ext_dev is the table in memory of
+        `device`, ext_host the host copy of it (an array of Extent) or None."""
+        m = (ctypes.c_size_t * len(masks))(*masks)
+        t = (ctypes.c_size_t * len(target_masks))(*target_masks)
+        return _check(lib.ec_method_heal_extents_device(
+            ctypes.byref(self._list), device, stream, nextents, ntiles, addr(ext_dev),
+            addr(ext_host), len(masks), m, t), "ec_method_heal_extents_device")
+
     def heal_device(self, device, stream, nstripes, mask, inp, target_mask, out):
         return _check(lib.ec_method_heal_device(ctypes.byref(self._list), device, stream,
                                                 nstripes, mask, _ptr_array(inp), target_mask,
@@ -888,6 +923,28 @@ class ECMatrixList:
         return _check(lib.ec_method_repair2_device(ctypes.byref(self._list), device, stream,
                                                    nstripes, avail_mask, _ptr_array(frags),
                                                    addr(loc)), "ec_method_repair2_device")
+
+
+def extent_table(records):
+    """An array of Extent from (frags, nstripes, pattern) records: frags is
+    indexed by brick (None or 0 for none).  `first` is left to extents_layout."""
+    table = (Extent * len(records))()
+    for r, (frags, nstripes, pattern) in zip(table, records):
+        for i, f in enumerate(frags):
+            r.frag[i] = addr(f) or 0
+        r.nstripes = nstripes
+        r.pattern = pattern
+    return table
+
+
+def extents_layout(table, nextents=None):
+    """ec_method_extents_layout: fills `first` of every record and returns the
+    number of tiles."""
+    n = len(table) if nextents is None else nextents
+    rc = lib.ec_method_extents_layout(n, addr(table))
+    if rc < 0:
+        _check(int(rc), "ec_method_extents_layout")
+    return rc
 
 
 def sync_device(device, stream=None):

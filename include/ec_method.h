@@ -985,6 +985,86 @@ int32_t ec_method_heal_mixed_device(ec_matrix_list_t *list, int device, void *st
                                     const uint8_t *group_pattern, uint32_t npatterns,
                                     const uintptr_t *masks, const uintptr_t *target_masks,
                                     void *const *frags);
+
+/* Fused heal of many files in one call: ec_method_heal_mixed for windows that
+ * arrive in buffers of their own (per-file reads, a pool of window buffers)
+ * and cannot be laid end to end in one allocation per brick.  An extent is
+ * one such window: nstripes stripes, the address of its fragment of every
+ * brick, and the pattern -- the pair (masks[pattern], target_masks[pattern])
+ * -- that heals it.  Its tiles of EC_MI355X_EXTENT_TILE stripes are numbered
+ * after those of all earlier extents: `first` is their count, which
+ * ec_method_extents_layout fills. */
+#define EC_MI355X_EXTENT_TILE 4u          /* stripes per tile of an extent */
+
+typedef struct {
+    uint64_t frag[EC_MI355X_MAX_NODES + 1]; /* frag[i]: address of this extent's fragment of
+                                               brick i (nstripes * 512 bytes), 0 = none */
+    uint32_t first;     /* tiles of all earlier extents: sum of ceil(nstripes / 4) */
+    uint32_t nstripes;  /* > 0 */
+    uint32_t pattern;   /* index into masks[] / target_masks[] */
+    uint32_t zero;      /* 0 */
+} ec_method_extent_t;   /* 272 bytes, no padding */
+
+/* Fill ext[e].first for e < nextents and return the total tile count.
+ * Returns 0 for nextents == 0, and -EINVAL for NULL, nstripes == 0, or a total
+ * above 2^31 - 1 (the table is then left as it was).  Needs no device. */
+int64_t ec_method_extents_layout(uint64_t nextents, ec_method_extent_t *ext);
+
+/* For every extent e, every stripe t < ext[e].nstripes and every brick i in
+ * target_masks[ext[e].pattern], chunk t of ext[e].frag[i] becomes what
+ * ec_method_heal gives for that stripe from the k bricks in
+ * masks[ext[e].pattern], read from ext[e].frag[].  Nothing else is written and
+ * source chunks are only read.  An extent whose pattern has an empty target
+ * mask is neither read nor written, and all of its frag[] may be 0.  Extents
+ * may come in any address order and may share source buffers that no extent
+ * writes; a target chunk of one extent that is a source or target chunk of
+ * another is undefined.
+ * Pattern u is (masks[u], target_masks[u]), host arrays, npatterns <= 256; the
+ * rules are those of ec_method_heal_mixed_device, and every pattern is checked
+ * whether an extent uses it or not.
+ * Host variant: ext and every fragment are host memory.  Runs on the calling
+ * thread's CPU engine whatever the volume's engine is, extent by extent, and
+ * leaves ec_method_get_stats alone: it is the byte-exact specification of the
+ * device call below.
+ * -EINVAL (with the reason in ec_method_last_error()): list, ext, masks or
+ * target_masks NULL; npatterns == 0; a bad pattern; a record with nstripes ==
+ * 0, a non-zero `zero`, a pattern at or above npatterns or a `first` that is
+ * not the running sum; more than 2^31 - 1 tiles; frag[i] == 0 for a brick in
+ * the mask or target mask of a pattern with targets; the table or such a
+ * fragment in device memory.  -E2BIG: npatterns above 256.  nextents == 0
+ * returns 0 after the pattern checks and touches nothing. */
+int32_t ec_method_heal_extents(ec_matrix_list_t *list, uint64_t nextents,
+                               const ec_method_extent_t *ext, uint32_t npatterns,
+                               const uintptr_t *masks, const uintptr_t *target_masks);
+
+/* ec_method_heal_extents on device buffers.  ext_dev: nextents records in
+ * memory of `device` (8-byte aligned) that hold addresses on `device`; ntiles:
+ * what ec_method_extents_layout returned for the table.  ext_host, when not
+ * NULL, is the caller's host copy of the same table: it is checked in full as
+ * the host call checks its table (fragments must be memory of `device`), and
+ * ntiles must be its total; the caller promises that ext_dev holds the same
+ * bytes.  ext_host == NULL is for tables written on the GPU: only the
+ * patterns, nextents <= ntiles <= 2^31 - 1 and the table's own address are
+ * checked, and a TABLE THAT BREAKS THE RULES ABOVE IS UNDEFINED BEHAVIOUR --
+ * wrong `first` or nstripes, a 0 or foreign address for a brick that the
+ * pattern names, overlapping targets.  Only a `pattern` at or above npatterns
+ * is defined: it is clamped to the last pattern, as group_pattern ids are.
+ * One launch of one kernel (ec_heal_extents_n, a block per tile, which finds
+ * its extent by a binary search of the table), asynchronous on `stream`: no
+ * host synchronisation, no allocation beyond the cached device table of a
+ * pattern set that does not fit the 2 KiB kernel arguments, no pre-zeroing,
+ * no atomics, and no block waits on another.  A call whose patterns all have
+ * empty targets launches nothing.  ext_dev and the fragments must stay as they
+ * are until the stream has run the call.  Non-temporal staging (calls that
+ * read more than 256 MiB from 16-byte aligned fragments) needs ext_host.
+ * -ENODEV where the device layer lacks the call; -EINVAL also for a table, a
+ * host copy or a fragment on the wrong side. */
+int32_t ec_method_heal_extents_device(ec_matrix_list_t *list, int device, void *stream,
+                                      uint64_t nextents, uint64_t ntiles,
+                                      const ec_method_extent_t *ext_dev,
+                                      const ec_method_extent_t *ext_host,
+                                      uint32_t npatterns, const uintptr_t *masks,
+                                      const uintptr_t *target_masks);
 int32_t ec_method_sync_device(int device, void *stream);
 
 /* ------------------------------------------------------------------------
